@@ -20,7 +20,18 @@ gradients in another (mitsuba_hip.distributed.fwd_grad_step).  Inside each
 call the library runs the fused wavefront's chunks on two streams (mh_api.hip
 fork_stream), so the kernel rooflines come from 2 steps with one stream
 (MH_WF_STREAMS=1) right after the timed region -- a timed launch shares the
-chip with the other chunk's (`roofline_timed`).  --overlap runs the forward
+chip with the other chunk's (`roofline_timed`).
+
+A plain run sets up, warms up, times --steps steps and prints the line
+(metric, value, unit, ms_per_step, ... and what the timed steps' own counters
+give).  --full adds what takes runs of its own: that one-stream roofline pass
+(roofline, roofline_other, roofline_splat, roofline_timed, one_stream_step,
+*_kernel_ms_one_stream) and the CPU baseline (cpu_baseline).  --dump-outputs
+DIR writes what the last timed step returned (image.npy and gradient.npy;
+film.npy or gradient.npy for configs 1 / 3 / 4) as float32; the step seeds
+are the step indices, so the inputs are the same from run to run.
+
+--overlap runs the forward
 and the gradient pass of a step concurrently instead (two scene handles,
 streams and host threads; valid here because grad_in = d mean(image) does
 not depend on the image).
@@ -30,7 +41,7 @@ TOTAL (strong scaling: rank r takes samples [1024 r / N, 1024 (r + 1) / N) of
 every pixel; the forward runs 2 passes of 512 spp, integrator.cpp:281-295, the
 gradient one AD wavefront of 2^32 samples), max_depth 8, same JSON line.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|5]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|5] [--full] [--dump-outputs DIR]
        torchrun --nproc-per-node N bench.py --gpus N ...   (the driver)
        torchrun --nproc-per-node 8 bench.py --gpus 8 --config 5
 
@@ -66,8 +77,16 @@ def parse(argv=None):
     p.add_argument("--res", type=int, default=512)
     p.add_argument("--spp", type=int, default=256, help="samples per pixel per GPU")
     p.add_argument("--max-depth", type=int, default=8)
-    p.add_argument("--cpu-seconds", type=float, default=24.0, help="budget of the CPU baseline (thread curve: 1, 4, all threads)")
-    p.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline (profiling runs)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run what the headline figure does not need: the one-stream "
+                        "roofline pass (2 more steps with MH_WF_STREAMS=1; the line's roofline* and one_stream_step "
+                        "fields) and the CPU baseline (cpu_baseline)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step returned as DIR/<name>.npy (float32; "
+                        "at most 64 MB in all, a seeded sample of a larger output)")
+    p.add_argument("--cpu-seconds", type=float, default=24.0,
+                   help="--full: budget of the CPU baseline (thread curve: 1, 4, all threads)")
+    p.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline (profiling runs)")
     p.add_argument("--fwd-only", action="store_true")
     p.add_argument("--local-weights", action="store_true",
                    help="every rank computes the whole W image (no W all-reduce; N x the W splat work)")
@@ -89,7 +108,42 @@ def parse(argv=None):
     p.add_argument("--backend", default="nccl",
                    help="torch.distributed backend for N > 1 ('nccl' = RCCL over xGMI; 'gloo' to rehearse "
                         "several ranks on one GPU)")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: write the arrays (name -> tensor or ndarray; None
+    entries are skipped) as outdir/<name>.npy in float32.  Arrays are written
+    whole while they fit into max_bytes in all; an array over its share (the
+    bytes left, split evenly over the arrays not yet written, smallest first)
+    is written as a 1-D sample of its flattened elements at sorted indices
+    drawn without replacement from numpy's default_rng(0) -- the same indices
+    for the same shape, so two runs' files compare element for element."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        if hasattr(a, "detach"):
+            a = a.detach().cpu().numpy()
+        host[name] = np.ascontiguousarray(a, dtype=np.float32)
+    left = max_bytes
+    todo = sorted(host, key=lambda n: host[n].nbytes)
+    for k, name in enumerate(todo):
+        a = host[name]
+        share = left // (len(todo) - k)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share // 4, replace=False))
+            a = a.reshape(-1)[idx]
+        left -= a.nbytes
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def _free_port():
@@ -504,6 +558,78 @@ def main():
                  "collective_calls_per_step": {k: round(v["calls_per_step"], 2) for k, v in sorted(colls.items())}}
     samples_step = world * H * W * args.spp
     value = samples_step / (ms_step / 1e3) / 1e6
+    line = None
+    if rank == 0:
+        avg_f = sum(fwd_ms) / len(fwd_ms)
+        avg_b = (sum(bwd_ms) / len(bwd_ms)) if not args.fwd_only else 0.0
+        n_local = H * W * args.spp
+        coll = ("RCCL" if args.backend == "nccl" else args.backend)
+        if overlap:
+            par = (f"sample-slab x{world}; forward || gradient pass (two scene handles, two HIP streams); {coll}" +
+                   (" local W" if args.local_weights else " all-reduce (W)") +
+                   " + all-reduce (film + gradient, one buffer)")
+        elif packed:
+            par = f"sample-slab x{world} + {coll} all-reduce (film + W, one packed buffer) + all-reduce (gradient)"
+        else:
+            par = (f"sample-slab x{world} + {coll}" +
+                   (" all-reduce (film)" if args.film_all_reduce else " reduce to rank 0 (film)") +
+                   (", local W" if args.local_weights else ", all-reduce (W)") + ", all-reduce (gradient)")
+        cfg5 = args.config == 5
+        line = {
+            "metric": "Msamples/s (pixels×spp/s) fwd + PRB grad, cornell_box 512²; 1/2/4/8 GPU",
+            "value": round(value, 2), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_step, 3), "higher_is_better": True,
+            "scaling": "strong" if cfg5 else "weak", "vs_baseline": None, "dtype": "f32",
+            "data": "synthetic (cornell_box scene, seeded PCG32)",
+            "config": {"workload": (f"config 5: cornell_box {W}x{H} @ {spp_total} spp total ({args.spp}/GPU; "
+                                    f"forward in 2 passes): path fwd (max_depth {args.max_depth})" if cfg5 else
+                                    f"cornell_box {W}x{H} @ {args.spp} spp/GPU: path fwd (max_depth {args.max_depth})")
+                                   + ("" if args.fwd_only else f" + prb backward wrt '{key}'"),
+                       "film": f"{W}x{H}", "spp_per_gpu": args.spp, "spp_total": spp_total,
+                       "parallelism": par,
+                       "step": ("overlapped: forward || gradient pass" if overlap else
+                                "serial: forward, then gradient pass; each call's fused-wavefront chunks on two "
+                                "streams (mh_api.hip fork_stream)"),
+                       "collectives_per_step": ((1 if args.local_weights else 2) if overlap else
+                                                2 if packed else (1 if args.fwd_only else (2 if args.local_weights else 3))),
+                       "collective_bytes": (dict(({} if args.local_weights else {"W": H * W * 4}),
+                                                 **{"film+gradient": H * W * 16 + 12}) if overlap else
+                                            {"film+W": H * W * 20, "gradient": 12} if packed else
+                                            {"film": H * W * 16, "W": 0 if args.local_weights else H * W * 4,
+                                             "gradient": 12})},
+            "fwd_kernel_ms": round(avg_f, 3), "bwd_kernel_ms": round(avg_b, 3),
+            "rays_closest_per_sample": round(st_f.rays_closest / max(1, n_local), 4),
+            "rays_shadow_per_sample": round(st_f.rays_shadow / max(1, n_local), 4),
+            "rays_closest_per_sample_prb": (round(st_b.rays_closest / max(1, n_local), 4)
+                                            if not args.fwd_only else None),
+            "rays_shadow_per_sample_prb": (round(st_b.rays_shadow / max(1, n_local), 4)
+                                           if not args.fwd_only else None),
+        }
+        if multi is not None:
+            line["multi_gpu"] = multi
+        if args.dump_outputs:  # the last timed step's return: the developed image, the gradient of `key`
+            dump_outputs(args.dump_outputs, {"image": img, "gradient": None if g is None else g[0]})
+    if args.full:
+        more = full_figures(args, w, rank, dev, dist_on, H, W, ms_step, samples_step, overlap)
+        if rank == 0:
+            line.update(more)
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    if dist_on:
+        dist.destroy_process_group()
+
+
+def full_figures(args, w, rank, dev, dist_on, H, W, ms_step, samples_step, overlap):
+    """--full, after the timed steps of config 2 / 5: the one-stream roofline
+    pass (every rank runs it) and, on rank 0, the rooflines and the CPU
+    baseline.  Returns rank 0's extra fields of the line (None elsewhere)."""
+    import torch
+    import torch.distributed as dist
+    from mitsuba_hip import _abi as A
+    from mitsuba_hip import distributed as D
+    scene, fwd, prb, key, ops, slab, fwd_slab, st_f, st_b = (
+        w[k] for k in ("scene", "fwd", "prb", "key", "ops", "slab", "fwd_slab", "st_f", "st_b"))
+    world = dist.get_world_size() if dist_on else 1
     # in the timed steps a bounce launch shares the chip with the other
     # chunk's launches (the library's two chunk streams) or with the other
     # pass's (--overlap) for most of its duration: its HIP-event time there is
@@ -562,8 +688,6 @@ def main():
         # (tools/profile_r2.sh: FETCH/WRITE corrected by the calib_fetch factors
         # for the kernel's access width; VALU issue = SQ_INSTS_VALU x 2 cycles /
         # (1024 SIMDs x launch time x measured clock)).
-        avg_f = sum(fwd_ms) / len(fwd_ms)
-        avg_b = (sum(bwd_ms) / len(bwd_ms)) if not args.fwd_only else 0.0
         n_local = H * W * args.spp
         pmc = {}
         # tools/profile_r2.sh of the latest round's build.  These counters are
@@ -664,58 +788,14 @@ def main():
                 d["sensor"]["film"]["width"] = d["sensor"]["film"]["height"] = 512
                 cscene = mi.load_dict(d)
             cpu = cpu_baseline(cscene, fwd, prb, key, args.spp, args.cpu_seconds, args.fwd_only)
-        coll = ("RCCL" if args.backend == "nccl" else args.backend)
-        if overlap:
-            par = (f"sample-slab x{world}; forward || gradient pass (two scene handles, two HIP streams); {coll}" +
-                   (" local W" if args.local_weights else " all-reduce (W)") +
-                   " + all-reduce (film + gradient, one buffer)")
-        elif packed:
-            par = f"sample-slab x{world} + {coll} all-reduce (film + W, one packed buffer) + all-reduce (gradient)"
-        else:
-            par = (f"sample-slab x{world} + {coll}" +
-                   (" all-reduce (film)" if args.film_all_reduce else " reduce to rank 0 (film)") +
-                   (", local W" if args.local_weights else ", all-reduce (W)") + ", all-reduce (gradient)")
-        cfg5 = args.config == 5
-        line = {
-            "metric": "Msamples/s (pixels×spp/s) fwd + PRB grad, cornell_box 512²; 1/2/4/8 GPU",
-            "value": round(value, 2), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_step, 3), "higher_is_better": True,
-            "scaling": "strong" if cfg5 else "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic (cornell_box scene, seeded PCG32)",
-            "config": {"workload": (f"config 5: cornell_box {W}x{H} @ {spp_total} spp total ({args.spp}/GPU; "
-                                    f"forward in 2 passes): path fwd (max_depth {args.max_depth})" if cfg5 else
-                                    f"cornell_box {W}x{H} @ {args.spp} spp/GPU: path fwd (max_depth {args.max_depth})")
-                                   + ("" if args.fwd_only else f" + prb backward wrt '{key}'"),
-                       "film": f"{W}x{H}", "spp_per_gpu": args.spp, "spp_total": spp_total,
-                       "parallelism": par,
-                       "step": ("overlapped: forward || gradient pass" if overlap else
-                                "serial: forward, then gradient pass; each call's fused-wavefront chunks on two "
-                                "streams (mh_api.hip fork_stream)"),
-                       "collectives_per_step": ((1 if args.local_weights else 2) if overlap else
-                                                2 if packed else (1 if args.fwd_only else (2 if args.local_weights else 3))),
-                       "collective_bytes": (dict(({} if args.local_weights else {"W": H * W * 4}),
-                                                 **{"film+gradient": H * W * 16 + 12}) if overlap else
-                                            {"film+W": H * W * 20, "gradient": 12} if packed else
-                                            {"film": H * W * 16, "W": 0 if args.local_weights else H * W * 4,
-                                             "gradient": 12})},
-            "fwd_kernel_ms": round(avg_f, 3), "bwd_kernel_ms": round(avg_b, 3),
+        return {
             "fwd_kernel_ms_one_stream": round(fwd_ms_serial, 3),
             "bwd_kernel_ms_one_stream": round(bwd_ms_serial, 3) if not args.fwd_only else None,
-            "rays_closest_per_sample": round(st_f.rays_closest / max(1, n_local), 4),
-            "rays_shadow_per_sample": round(st_f.rays_shadow / max(1, n_local), 4),
-            "rays_closest_per_sample_prb": (round(st_b.rays_closest / max(1, n_local), 4)
-                                            if not args.fwd_only else None),
-            "rays_shadow_per_sample_prb": (round(st_b.rays_shadow / max(1, n_local), 4)
-                                           if not args.fwd_only else None),
             "roofline": roofline, "roofline_other": roofline_other, "roofline_splat": roofline_splat,
             "roofline_timed": roofline_timed, "one_stream_step": serial,
             "cpu_baseline": cpu,
         }
-        if multi is not None:
-            line["multi_gpu"] = multi
-        print(json.dumps(line), flush=True)
-    if dist_on:
-        dist.destroy_process_group()
+    return None
 
 
 def main_single_op(args, rank, world, dev, dist_on):
@@ -733,7 +813,7 @@ def main_single_op(args, rank, world, dev, dist_on):
     kms = []
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(i)
+        out = step(i)
         kms.append(st.ms_kernel)
     torch.cuda.synchronize()
     if dist_on:
@@ -746,9 +826,12 @@ def main_single_op(args, rank, world, dev, dist_on):
     # streams (mh_api.hip fork_stream), so a timed launch shares the chip with
     # the other chunk's; the rooflines come from 2 one-stream steps
     # (MH_WF_STREAMS=1) right after the timed region, the timed figures sit
-    # beside them (roofline_two_streams)
+    # beside them (roofline_two_streams).  --full only; config 4's roofline
+    # (one k_vol_sched launch per render) comes from the timed steps themselves
     st_timed = A.Stats.from_buffer_copy(st)
-    if args.config in (1, 3):
+    if rank == 0 and args.dump_outputs:  # the last timed step's return: the summed film, or the bitmap gradient
+        dump_outputs(args.dump_outputs, {"gradient" if args.config == 3 else "film": out})
+    if args.full and args.config in (1, 3):
         old = os.environ.get("MH_WF_STREAMS")
         os.environ["MH_WF_STREAMS"] = "1"
         try:
@@ -763,7 +846,7 @@ def main_single_op(args, rank, world, dev, dist_on):
     if rank == 0:
         n_local = res * res * spp
         roof = roof_other = two = None
-        if args.config == 3 and st.n_aux_launches:
+        if args.config == 3 and args.full and st.n_aux_launches:
             roof, roof_other = bitmap_rooflines(st, n_local, 64 * 64 * 3)  # config 3(b): a 64^2 x 3 bitmap
             note = "one-stream pass: 2 steps with MH_WF_STREAMS=1 right after the timed region"
             roof["measured"] = roof_other["measured"] = note
@@ -785,7 +868,7 @@ def main_single_op(args, rank, world, dev, dist_on):
                     roof["valu_issue_frac"] = round(k["valu_issue_frac"], 4)
                     roof["traffic_source"] = ("profiles/r6_pmc_config4.json @ " + pj.get("source", "") +
                                               " (not measured in this run)")
-        elif args.config == 1 and st.mode == 2:
+        elif args.config == 1 and args.full and st.mode == 2:
             def c1_roofs(s):
                 launches = max(1, s.n_trace_launches)
                 R, N = float(s.rays_closest), float(n_local)
@@ -802,7 +885,7 @@ def main_single_op(args, rank, world, dev, dist_on):
                 two = {"measured": "the timed region: the two chunks on two streams, each launch sharing the chip",
                        "kernels": [{k: r[k] for k in ("kernel", "achieved", "frac", "kernel_avg_us",
                                                       "launches_per_step")} for r in (tb, ts)]}
-        cpu = None if (args.no_cpu or world > 1) else cpu_single_op(args, scene, integ, res, spp)
+        cpu = None if (not args.full or args.no_cpu or world > 1) else cpu_single_op(args, scene, integ, res, spp)
         names = {1: "path fwd", 3: "PRB grad (bitmap albedo)", 4: "volpath fwd"}
         line = {
             "metric": f"Msamples/s (pixels×spp/s) {names[args.config]}, BASELINE config {args.config}",
