@@ -215,6 +215,7 @@ MH_DEV uint32_t lane_id() { return threadIdx.x & 63u; }
 // after the closest trace are paid in shade).  Read by mh_exp_bphase.
 #ifdef MH_EXP_BPHASE
 __device__ unsigned long long g_bph[4][12];
+static size_t g_prb_ring_lds = 0;  // dynamic LDS of the last rgb PRB bounce launches (mh_exp_prb_occupancy)
 #define MH_BPH_DECL uint64_t bph_t = __builtin_amdgcn_s_memtime(); uint64_t bph[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #define MH_BPH(k) do { const uint64_t _t = __builtin_amdgcn_s_memtime(); bph[k] += _t - bph_t; bph_t = _t; } while (0)
 #define MH_BPH_ITER() (bph[6] += 1)
@@ -1220,6 +1221,44 @@ static WfBmp carve_bmp(void *ws, uint64_t cap, uint32_t n_depth, int32_t slot) {
 #ifndef MH_BOUNCE_BMP_WAVES
 #define MH_BOUNCE_BMP_WAVES 4  // the Bm instance carries ~20 more live values across the shadow trace
 #endif
+// ---------------------------------------------------------------------------
+// NEE ring of the non-generating rgb PRB bounce (NR == 1, no Gen / Bm / Det).
+// About 70 % of a wave's lanes hold a shadow ray after an iteration, and a
+// packet trace costs the same whatever the number of live lanes.  In this
+// instance the shadow ray's only effect is acc += G, a sum over the whole
+// block that belongs to no path, so the rays of several iterations can be
+// traced together: an iteration whose rays still fit pushes them (ray and G,
+// 10 dwords) into the wave's LDS ring and skips the trace; one whose rays do
+// not fit fills its idle lanes from the ring and traces a full packet.  The
+// ring is private to the wave (wave-level ordering only), stored field-major
+// so that a push or pop of consecutive slots hits consecutive banks.
+// ---------------------------------------------------------------------------
+#ifndef MH_PRB_NEE_RING
+#define MH_PRB_NEE_RING 1
+#endif
+constexpr uint32_t kNeeRingFields = 10;                          // o, d, maxt, G[0][0..2]
+constexpr uint32_t kNeeRingFloats = kNeeRingFields * 64u;        // per wave (slot 63 is never used)
+template <int NR, bool Gen, bool Bm, bool Det>
+constexpr bool prb_nee_ring() { return MH_PRB_NEE_RING && NR == 1 && !Gen && !Bm && !Det; }
+MH_DEV void nee_ring_put(float *ring, uint32_t slot, const RayT &r, const float (&g)[3]) {
+    ring[0 * 64 + slot] = r.o.x; ring[1 * 64 + slot] = r.o.y; ring[2 * 64 + slot] = r.o.z;
+    ring[3 * 64 + slot] = r.d.x; ring[4 * 64 + slot] = r.d.y; ring[5 * 64 + slot] = r.d.z;
+    ring[6 * 64 + slot] = r.maxt;
+    ring[7 * 64 + slot] = g[0]; ring[8 * 64 + slot] = g[1]; ring[9 * 64 + slot] = g[2];
+}
+MH_DEV void nee_ring_get(const float *ring, uint32_t slot, RayT &r, float (&g)[3]) {
+    r.o = v3(ring[0 * 64 + slot], ring[1 * 64 + slot], ring[2 * 64 + slot]);
+    r.d = v3(ring[3 * 64 + slot], ring[4 * 64 + slot], ring[5 * 64 + slot]);
+    r.maxt = ring[6 * 64 + slot];
+    g[0] = ring[7 * 64 + slot]; g[1] = ring[8 * 64 + slot]; g[2] = ring[9 * 64 + slot];
+}
+// LDS written by some lanes of the wave is read by others
+MH_DEV void nee_ring_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 template <int NR, bool Gen, bool Bm, bool Det>
 __global__ void __launch_bounds__(256, Bm ? MH_BOUNCE_BMP_WAVES : MH_BOUNCE_PRB_WAVES)
 k_wf_bounce_prb(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value, WfState w, WfPrb q,
@@ -1244,6 +1283,14 @@ k_wf_bounce_prb(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value,
                    (threadIdx.x >> 6) * S0.stack_size;
     uint8_t *dscr = reinterpret_cast<uint8_t *>(lds) + fused_scratch_offset(S0) + (threadIdx.x >> 6) * kDeferScratch;
     uint32_t n_shadow = 0;
+    constexpr bool Ring = prb_nee_ring<NR, Gen, Bm, Det>();
+    // the wave's NEE ring, behind the deferral scratch (the launch adds 4 * kNeeRingFloats floats);
+    // the wave index through readfirstlane: a scalar base (as a VGPR it was spilled)
+    float *ring = nullptr;
+    if constexpr (Ring)
+        ring = reinterpret_cast<float *>(reinterpret_cast<uint8_t *>(lds) + fused_lds_bytes(S0)) +
+               __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * kNeeRingFloats;
+    uint32_t ring_n = 0;  // items in the ring (wave-uniform)
     const int nxt = cur ^ 1;
     const uint32_t n_rgb = q.n_rgb;
     float acc[NR][3];
@@ -1457,6 +1504,27 @@ k_wf_bounce_prb(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value,
         }
         // ---- visibility of the NEE sample; the record is charged if unoccluded
         MH_BPH(3);
+        if constexpr (Ring) {
+            const unsigned long long sm = __ballot(shadow);
+            const uint32_t k = (uint32_t)__popcll(sm);
+            n_shadow += k;  // counted where the ray is produced
+            if (ring_n + k < 64u && itr + 1u != n_iter) {  // they fit: push, no trace
+                if (shadow) nee_ring_put(ring, ring_n + lane_rank(sm), sray, G[0]);
+                ring_n += k;
+                MH_BPH(4);
+                MH_BPH(5);
+                continue;
+            }
+            // idle lanes take an item each, then one full packet
+            const uint32_t take = std::min(ring_n, 64u - k), fr = lane_rank(~sm);
+            nee_ring_sync();
+            if (!shadow && fr < take) {
+                nee_ring_get(ring, ring_n - 1u - fr, sray, G[0]);
+                shadow = true;
+            }
+            ring_n -= take;
+            nee_ring_sync();
+        }
         const Hit sh = packet_batch<true, true, Gen>(S0.nodes, S0.prims, S0.prim_pairs, S0.key_sp, ws, 1u, sray, shadow, recs, dscr);
         MH_BPH(4);
         const bool unocc = shadow && sh.shape == MH_INVALID;
@@ -1499,8 +1567,25 @@ k_wf_bounce_prb(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value,
                 if (vmask) bm.fin[bm.stride + pid] = make_float4(dL.x, dL.y, dL.z, 0.f);
             }
         }
-        n_shadow += (uint32_t)__popcll(__ballot(shadow));
+        if constexpr (!Ring) n_shadow += (uint32_t)__popcll(__ballot(shadow));
         MH_BPH(5);
+    }
+    if constexpr (Ring) {  // what the last iteration's packet had no room for
+        while (ring_n) {
+            const uint32_t take = std::min(ring_n, 64u);
+            const bool has = lane_id() < take;
+            RayT sray{v3(0, 0, 0), v3(0, 0, 1), -1.f};
+            float g[3] = {0.f, 0.f, 0.f};
+            nee_ring_sync();
+            if (has) nee_ring_get(ring, ring_n - 1u - lane_id(), sray, g);
+            ring_n -= take;
+            const Hit sh = packet_batch<true, true, false>(S0.nodes, S0.prims, S0.prim_pairs, S0.key_sp, ws, 1u, sray, has, recs, dscr);
+            if (has && sh.shape == MH_INVALID && n_rgb) {
+                acc[0][0] += g[0];
+                acc[0][1] += g[1];
+                acc[0][2] += g[2];
+            }
+        }
     }
     if (lane_id() == 0 && n_shadow) atomicAdd(ctr + it.seg * 32 + 1, n_shadow);  // statistics only
     flush_partial(acc, q);
@@ -2020,10 +2105,13 @@ hipError_t launch_wavefront_prb(const DScene &S, const IntegratorParams &in, con
                            seed_value, n, coalesce, grad_in, weights, w, q, ctr);
     const PrbGen gen{n, grad_in, coalesce};
     if (span) (void)hipEventRecord(span[0], st);
+#ifdef MH_EXP_BPHASE
+    g_prb_ring_lds = sh_fused + (prb_nee_ring<1, false, false, false>() ? 4u * kNeeRingFloats * 4u : 0u);
+#endif
 #define MH_BOUNCE_PRB(NR, GEN, BM, DET)                                                                        \
     hipLaunchKernelGGL((k_wf_bounce_prb<NR, GEN, BM, DET>),                                                    \
                        dim3(grid), dim3(256),      \
-                       sh_fused, st, S, in, lm, seed_value, w, q, cur, seg_cap, c, cn, gen, bm, det)
+                       sh_fused + (prb_nee_ring<NR, GEN, BM, DET>() ? 4u * kNeeRingFloats * 4u : 0u), st, S, in, lm, seed_value, w, q, cur, seg_cap, c, cn, gen, bm, det)
 #define MH_BOUNCE_PRB_NR(GEN, BM, DET)                                                                         \
     do {                                                                                                       \
         if (n_rgb <= 1) MH_BOUNCE_PRB(1, GEN, BM, DET);                                                        \
@@ -2159,6 +2247,15 @@ hipError_t launch_wf_grad_reduce(const float *partial, uint32_t grid, uint32_t n
 }
 
 #ifdef MH_EXP_BPHASE
+// workgroups of k_wf_bounce_prb<1, false, false, false> a CU holds at the
+// dynamic LDS of its last launch (*lds_bytes); < 0: the query failed
+extern "C" int mh_exp_prb_occupancy(unsigned long long *lds_bytes) {
+    int r = -1;
+    if (lds_bytes) *lds_bytes = g_prb_ring_lds;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&r, k_wf_bounce_prb<1, false, false, false>, 256, g_prb_ring_lds) != hipSuccess)
+        return -1;
+    return r;
+}
 extern "C" int mh_exp_bphase(unsigned long long *out, int reset) {
     hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bph), sizeof(g_bph));
     if (reset) {

@@ -65,6 +65,15 @@ def main():
             print(f"    {p:15s} {x / tot:6.3f}  {x / iters:8.0f} cycles/iteration")
         out[name] = {"iterations": iters, "cycles_per_iteration": tot / iters,
                      "share": {p: x / tot for p, x in zip(names, vals)}}
+    # the rgb PRB bounce with its NEE ring: workgroups per CU at the dynamic LDS of the launches above
+    occ = getattr(_abi.lib(), "mh_exp_prb_occupancy", None)
+    if occ is not None:
+        occ.argtypes = [C.POINTER(C.c_ulonglong)]
+        lds = C.c_ulonglong(0)
+        n = occ(C.byref(lds))
+        print(f"k_wf_bounce_prb<1,false,false,false>: {n} workgroups per CU at {lds.value} B of dynamic LDS "
+              "(hipOccupancyMaxActiveBlocksPerMultiprocessor)")
+        out["prb_ring_occupancy"] = {"workgroups_per_cu": n, "dynamic_lds_bytes": lds.value}
     print(json.dumps(out))
 
 
