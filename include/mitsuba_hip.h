@@ -109,8 +109,11 @@ enum {
     MH_FLAG_MEGAKERNEL      = 1u << 3,  /* mh_render: force the per-lane megakernel */
     MH_FLAG_WAVEFRONT       = 1u << 4,  /* mh_render: force the wavefront (trace/shade/shadow) kernels */
     MH_FLAG_PRB_REPLAY      = 1u << 5,  /* mh_render_backward: primal + adjoint replay even for rgb params */
-    MH_FLAG_DETERMINISTIC   = 1u << 6,  /* film / W-image splat as a fixed-order gather instead of float
-                                           atomics: bit-reproducible films; mh_render_backward on the fused
+    MH_FLAG_DETERMINISTIC   = 1u << 6,  /* film / W-image / alpha splat as a fixed-order gather instead of
+                                           float atomics: bit-reproducible films -- for the Gaussian filter
+                                           with 1.5 < radius <= 2.5 at >= 4 spp per pass only; any other
+                                           filter (box, other radii) or spp splats with float atomics, whose
+                                           order is not fixed; mh_render_backward on the fused
                                            wavefront: rgb gradients summed per path and reduced in path-id
                                            order, and bitmap texels in int64 fixed point (a max pass sizes
                                            the scale), bit-reproducible; prbvolpath gradients (grid sigma_t

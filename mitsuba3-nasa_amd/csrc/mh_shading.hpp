@@ -1329,7 +1329,8 @@ MH_DEV void bitmap_taps(const DTexture &tx, float uvx, float uvy, Taps &tp) {
         int32_t ix = wrap_index((int32_t)floorf(ux * (float)W), W, tx.wrap);
         int32_t iy = wrap_index((int32_t)floorf(uy * (float)H), H, tx.wrap);
         tp.n = 1;
-        tp.idx[0] = tx.data_offset + ((uint64_t)iy * W + ix) * C;
+        // one tap; idx[1..3] repeat it so that no caller indexes an unset offset
+        tp.idx[0] = tp.idx[1] = tp.idx[2] = tp.idx[3] = tx.data_offset + ((uint64_t)iy * W + ix) * C;
         tp.w0x = tp.w0y = 1.f;
         tp.w1x = tp.w1y = 0.f;
         return;
@@ -2044,10 +2045,27 @@ MH_DEV V3 gather_dL(const DScene &S, int coalesce, const float *__restrict__ gw,
     const float radius = S.rfilter_radius;
     if (coalesce) {
         int32_t nn = (int32_t)ceilf(radius - 0.5f), count = 2 * nn + 1;
-        if (count > 5) count = 5;  // radius <= 2.5 (host-checked for this path)
         int32_t pix = (int32_t)floorf(px) - nn, piy = (int32_t)floorf(py) - nn;
         float relx = ((float)pix + 0.5f) - px, rely = ((float)piy + 0.5f) - py;
-        float wxs[5];
+        if (count > 5) {  // radius > 2.5: the whole 2 nn + 1 footprint, as k_splat_generic splats it
+            for (int32_t ys = 0; ys < count; ++ys) {
+                float wy = gaussian_eval(S.filter_coeff, rely + (float)ys);
+                uint32_t yy = (uint32_t)(piy + ys);
+                if (yy >= H) continue;
+                for (int32_t xs = 0; xs < count; ++xs) {
+                    uint32_t xx = (uint32_t)(pix + xs);
+                    if (xx < W) {
+                        const float4 g = g4[(uint64_t)yy * W + xx];
+                        float w = wy * gaussian_eval(S.filter_coeff, relx + (float)xs);
+                        o0 += g.x * w;
+                        o1 += g.y * w;
+                        o2 += g.z * w;
+                    }
+                }
+            }
+            return v3(o0, o1, o2);
+        }
+        float wxs[5];  // count <= 5: unrolled
 #pragma unroll
         for (int32_t xs = 0; xs < 5; ++xs) wxs[xs] = xs < count ? gaussian_eval(S.filter_coeff, relx + (float)xs) : 0.f;
 #pragma unroll

@@ -184,7 +184,9 @@ def render_film(scene: Scene, integrator: Optional[Integrator] = None, seed: int
     """Integrator::render(develop=False): RGBW film (H, W, 4) on the device.
     mode: 'auto' (wavefront for `path`), 'mega' (per-lane megakernel) or 'wavefront'.
     deterministic: splat as a fixed-order gather (bit-reproducible film) instead
-    of float atomics.  stats.invalid_samples counts samples with a non-finite
+    of float atomics -- for the Gaussian filter with 1.5 < radius <= 2.5 at
+    >= 4 spp per pass; other filters or spp keep the float atomics
+    (MH_FLAG_DETERMINISTIC, include/mitsuba_hip.h).  stats.invalid_samples counts samples with a non-finite
     or negative channel (ImageBlock::put's warn_invalid / warn_negative test).
     shared: another call runs on the device at the same time
     (MH_FLAG_SHARED_DEVICE, a performance hint; the result is unchanged)."""

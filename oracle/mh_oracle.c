@@ -739,7 +739,8 @@ static void bitmap_taps(const mh_texture *tx, float uvx, float uvy, tex_taps *tp
         int32_t ix = wrap_index((int32_t)floorf(ux * (float)W), W, tx->wrap);
         int32_t iy = wrap_index((int32_t)floorf(uy * (float)H), H, tx->wrap);
         tp->n = 1;
-        tp->idx[0] = tx->data_offset + ((uint64_t)iy * W + ix) * C;
+        /* one tap; idx[1..3] repeat it so that no caller indexes an unset offset */
+        tp->idx[0] = tp->idx[1] = tp->idx[2] = tp->idx[3] = tx->data_offset + ((uint64_t)iy * W + ix) * C;
         tp->w0x = tp->w0y = 1.f;
         tp->w1x = tp->w1y = 0.f;
         return;
@@ -778,6 +779,17 @@ static v3 tex_eval(const mh_scene_desc *d, uint32_t tex, float uvx, float uvy) {
         }
     }
     return V3(out[0], out[1], out[2]);
+}
+
+/* test hook: tex_eval at n uv pairs (tests/test_bitmap_oracle.py) */
+int oracle_tex_eval(const mh_scene_desc *desc, uint32_t tex, uint64_t n, const float *uv, float *out) {
+    if (!desc || !uv || !out) return fail("oracle_tex_eval: null argument");
+    if (tex >= desc->n_textures) return fail("oracle_tex_eval: texture index out of range");
+    for (uint64_t i = 0; i < n; ++i) {
+        v3 c = tex_eval(desc, tex, uv[2 * i], uv[2 * i + 1]);
+        out[3 * i] = c.x; out[3 * i + 1] = c.y; out[3 * i + 2] = c.z;
+    }
+    return 0;
 }
 
 /* Gradient sink: d(loss)/d(texture parameter) accumulators (double) */

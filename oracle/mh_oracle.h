@@ -41,6 +41,8 @@ float oracle_exp(float x);
 void  oracle_diffuse_eval_pdf(const float wi[3], const float wo[3], const float rho[3],
                               float value[3], float *pdf);
 void  oracle_square_to_cosine_hemisphere(const float s[2], float out[3]);
+/* tex_eval of texture `tex` at n surface uv (u, v interleaved): out = 3 n floats */
+int   oracle_tex_eval(const mh_scene_desc *desc, uint32_t tex, uint64_t n, const float *uv, float *out);
 
 /* --- ray queries (brute force over shapes; SoA rays like mh_trace_*) ---- */
 int oracle_trace_closest(const mh_scene_desc *desc, uint64_t n, const float *rays, float *t,

@@ -87,8 +87,58 @@ def diffuse():
             "pdf": "cos(theta) / pi", "eval": "0.5 * cos(theta) / pi", "source": f"{path}:13-35"}
 
 
+def bitmap_wrap():
+    """The uv ranges and tolerances of the reference's wrap-mode properties
+    (test03_wrap): a 20 x 20 grid over [0, 1]^2 against the same grid moved
+    by one period (repeat), clamped to an edge row / column (clamp) or
+    reflected (mirror: the reversed ranges)."""
+    path = "src/textures/tests/test_bitmap.py"
+    L = _lines(path)
+    start = next(i for i, ln in enumerate(L, 1) if "def test03_wrap" in ln)
+    end = next(i for i, ln in enumerate(L, 1) if i > start and ln.startswith("def "))
+    lin = re.compile(r"\b(x|y) = dr\.linspace\(mi\.Float, (-?\d+), (-?\d+), axis_res\)(\[::-1\])?")
+    edges = {"Top": ("row", 0, "[:axis_res]"), "Bottom": ("row", -1, "[-axis_res:]"),
+             "Left": ("column", 0, "[::axis_res]"), "Right": ("column", -1, "[axis_res - 1::axis_res]")}
+    out = {"repeat": [], "clamp": [], "mirror": []}
+    mode, name, cur, first = None, None, {}, None
+    for i in range(start, end):
+        ln = L[i - 1]
+        m = re.search(r"axis_res = (\d+)", ln)
+        if m:
+            out["axis_res"] = int(m.group(1))
+        m = re.search(r"wrap_mode == '(\w+)'", ln)
+        if m:
+            mode = m.group(1)
+        m = re.match(r"\s*# (.+)$", ln)
+        if m:
+            name = m.group(1).strip()
+        m = lin.search(ln)
+        if m:
+            cur[m.group(1)] = [float(m.group(2)), float(m.group(3))]
+            cur["reversed_" + m.group(1)] = bool(m.group(4))
+            if m.group(1) == "x":
+                first = i
+            if mode is None and m.group(1) == "y":
+                out["ref"] = {"x": cur["x"], "y": cur["y"], "source": f"{path}:{first}-{i + 1}"}
+        m = re.search(r"atol=([0-9.e+-]+)\)", ln)
+        if m and mode:
+            case = {"name": name, "x": cur["x"], "y": cur["y"],
+                    "reversed": cur["reversed_x"] and cur["reversed_y"], "atol": float(m.group(1)),
+                    "source": f"{path}:{first}-{i}"}
+            assert cur["reversed_x"] == cur["reversed_y"]
+            if mode == "clamp":
+                axis, index, slc = edges[name]
+                assert any(slc in s for s in L[first - 1:i]), (name, slc)
+                case["equals"] = {"axis": axis, "index": index}
+            out[mode].append(case)
+    assert out["axis_res"] == 20 and [len(out[k]) for k in ("repeat", "clamp", "mirror")] == [2, 4, 2]
+    out["source"] = f"{path}:{start - 1}-{end - 4} (test03_wrap)"
+    return out
+
+
 def known_answers():
     return {
+        "bitmap_wrap": bitmap_wrap(),
         "tea": tea_table(),
         "gaussian": gaussian(),
         "rectangle": rectangle(),

@@ -38,6 +38,7 @@ def lib():
     L.oracle_log.restype = C.c_float
     L.oracle_diffuse_eval_pdf.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_float)]
     L.oracle_square_to_cosine_hemisphere.argtypes = [vp, vp]
+    L.oracle_tex_eval.argtypes = [C.POINTER(A.SceneDesc), C.c_uint32, C.c_uint64, vp, vp]
     L.oracle_trace_closest.argtypes = [C.POINTER(A.SceneDesc), C.c_uint64, vp, vp, vp, vp, vp, vp]
     L.oracle_trace_shadow.argtypes = [C.POINTER(A.SceneDesc), C.c_uint64, vp, vp]
     L.oracle_camera_ray.argtypes = [C.POINTER(A.SceneDesc), vp, vp, vp, C.POINTER(C.c_float)]
@@ -135,6 +136,14 @@ def sample_range(scene, integrator, seed, spp, begin, end):
     check(lib().oracle_sample_range(C.byref(scene.desc), C.byref(ic), seed, spp, begin, end,
                                     _p(L), _p(pos), _p(valid)))
     return L, pos, valid
+
+
+def tex_eval(scene, tex, uv):
+    """tex_eval of texture index `tex` at the (n, 2) surface uv: (n, 3) rgb."""
+    uv = np.ascontiguousarray(uv, np.float32)
+    out = np.zeros((uv.shape[0], 3), np.float32)
+    check(lib().oracle_tex_eval(C.byref(scene.desc), tex, uv.shape[0], _p(uv), _p(out)))
+    return out
 
 
 def trace_closest(scene, rays):
