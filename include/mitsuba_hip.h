@@ -14,7 +14,8 @@
  *   mh_scene_create / mh_scene_destroy
  *       Scene::Scene + accel_init_gpu (OptiX GAS/IAS build)
  *       src/render/scene.cpp:22-96, src/render/scene_optix.inl:304-547
- *   mh_scene_update_texture / mh_scene_update_rgb / mh_scene_update_medium
+ *   mh_scene_update_texture / mh_scene_update_rgb / mh_scene_update_medium /
+ *   mh_scene_update_emitter
  *       SceneParameters.update -> Scene::parameters_changed
  *       src/python/python/util.py:292-350, src/render/scene.cpp:481-529
  *   mh_render
@@ -87,16 +88,22 @@ enum { MH_MEDIUM_NO_EMITTER_SAMPLING = 1u,        /* medium.cpp:29 sample_emitte
 enum { MH_INTEGRATOR_PATH = 0, MH_INTEGRATOR_VOLPATH = 1, MH_INTEGRATOR_PRB = 2,
        MH_INTEGRATOR_PRBVOLPATH = 3 };                        /* python/ad/integrators/prbvolpath.py */
 
-/* Differentiable parameter ids of mh_render_backward (param_textures[]):
- * a texture index (kind 0: '<bsdf>.reflectance.value' / '.data'), or a kind
- * tag | medium index.  Medium parameters need MH_INTEGRATOR_PRBVOLPATH.
+/* Differentiable parameter ids of mh_render_backward / mh_render_forward
+ * (param_textures[]): a texture index (kind 0: '<bsdf>.reflectance.value' /
+ * '.data'), or a kind tag | medium or emitter index.  Medium parameters need
+ * MH_INTEGRATOR_PRBVOLPATH; emitter parameters take either integrator.
  *   MH_PARAM_MEDIUM_SIGMA_T | m : '<medium>.sigma_t.data' (heterogeneous grid,
  *                                 res_x*res_y*res_z floats) or '.value'
  *                                 (homogeneous, 1 float)
- *   MH_PARAM_MEDIUM_ALBEDO | m  : '<medium>.albedo.value' (3 floats)        */
+ *   MH_PARAM_MEDIUM_ALBEDO | m  : '<medium>.albedo.value' (3 floats)
+ *   MH_PARAM_EMITTER_RADIANCE | e : mh_emitter::radiance of emitter e (3 floats):
+ *                                 '<shape>.emitter.radiance.value' (area),
+ *                                 '<name>.radiance.value' (constant) or
+ *                                 '<name>.irradiance.value' (directional)    */
 #define MH_PARAM_KIND_MASK      0xF0000000u
 #define MH_PARAM_MEDIUM_SIGMA_T 0x10000000u
 #define MH_PARAM_MEDIUM_ALBEDO  0x20000000u
+#define MH_PARAM_EMITTER_RADIANCE 0x30000000u
 
 /* Flags for mh_render / mh_render_backward / mh_trace_*                   */
 enum {
@@ -305,6 +312,12 @@ int mh_scene_update_rgb(mh_scene *scene, uint32_t texture, const float value[3])
 int mh_scene_update_medium(mh_scene *scene, uint32_t medium, const float *albedo, const float *sigma_t,
                            const float *grid, uint64_t n, uint32_t flags);
 int mh_scene_update_texture(mh_scene *scene, uint32_t texture, const float *data, uint64_t n_floats);
+/* An emitter's radiance (area / constant) or irradiance (directional), 3
+ * floats (host): traverse()/update() of '<shape>.emitter.radiance.value',
+ * '<name>.radiance.value' and '<name>.irradiance.value'.  Same contract as
+ * mh_scene_update_rgb: MH_ERR_INVALID_ARGUMENT for a NULL argument or an
+ * emitter index out of bounds; ordered on the scene's stream. */
+int mh_scene_update_emitter(mh_scene *scene, uint32_t emitter, const float radiance[3]);
 
 /*
  * Forward render into the un-developed film storage: RGBW (H*W*4 floats), or
@@ -343,7 +356,8 @@ int mh_develop(mh_scene *scene, const float *film_rgbw, float *image_rgb, uint32
 /*
  * Reverse-mode derivative of render(): accumulates d(loss)/d(param) for each
  * listed parameter into grads[k] (3 floats for MH_TEX_RGB, W*H*C for
- * MH_TEX_BITMAP; medium ids: see MH_PARAM_*).  `grad_in` is d(loss)/d(rgb
+ * MH_TEX_BITMAP; medium and emitter ids: see MH_PARAM_*; an emitter's
+ * radiance, 3 floats, with either integrator).  `grad_in` is d(loss)/d(rgb
  * before the colour conversion of develop), H*W*3: the caller applies the
  * adjoint of luminance / srgb_to_xyz and drops the alpha channel, whose
  * value (a validity mask) carries no derivative.  integrator: MH_INTEGRATOR_PRB (prb.py) or MH_INTEGRATOR_PRBVOLPATH
@@ -366,7 +380,8 @@ int mh_render_backward(mh_scene *scene, const mh_integrator *integrator, uint32_
  * Forward-mode derivative of render(): RBIntegrator.render_forward
  * (src/python/python/ad/integrators/common.py:696-826).  tangents[k] holds
  * the input tangent of parameter param_textures[k] (same shape and ids as
- * mh_render_backward's grads[k]; host or device per flags).  The sample's
+ * mh_render_backward's grads[k], MH_PARAM_EMITTER_RADIANCE included; host or
+ * device per flags).  The sample's
  * tangent radiance dL (prb.py:244-248, `δL += dr.forward_to(Lo)`) is splatted
  * like a primal sample, value = dL, weight 1 and alpha = the ray validity
  * (common.py:799-806), into the film storage of mh_render (RGBW, or R G B A W

@@ -133,6 +133,7 @@ struct mh_scene {
     std::vector<DTexture> h_textures;
     std::vector<mh_medium> h_media;
     std::vector<DMedium> h_dmedia;
+    std::vector<DEmitter> h_emitters;
     uint32_t n_textures = 0, n_bsdfs = 0, n_shapes = 0, n_media = 0, pixel_format = MH_PIXEL_RGB;
     uint64_t n_texels = 0;
     uint32_t bvh_nodes = 0, bvh_prims = 0, bvh_depth = 0;
@@ -384,7 +385,8 @@ int mh_scene_create(const mh_scene_desc *desc, int device, void *stream, mh_scen
             a.data_offset + (uint64_t)a.width * a.height * a.channels > desc->n_texels)
             return fail(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: bitmap data out of bounds");
     }
-    std::vector<DEmitter> ems(desc->n_emitters);
+    std::vector<DEmitter> &ems = s->h_emitters;
+    ems.resize(desc->n_emitters);
     for (uint32_t i = 0; i < desc->n_emitters; ++i) {
         memset(&ems[i], 0, sizeof(DEmitter));
         ems[i].type = desc->emitters[i].type;
@@ -597,6 +599,20 @@ int mh_scene_update_rgb(mh_scene *s, uint32_t tex, const float value[3]) {
     MH_HIP(hipSetDevice(s->device));
     memcpy(s->h_textures[tex].value, value, 12);
     MH_HIP(hipMemcpyAsync(s->textures.as<DTexture>() + tex, &s->h_textures[tex], sizeof(DTexture),
+                          hipMemcpyHostToDevice, s->stream));
+    MH_HIP(hipStreamSynchronize(s->stream));
+    return MH_OK;
+}
+
+// SceneParameters.update of an emitter's radiance / irradiance: the DEmitter
+// table behind DScene::emitters (staged into LDS per launch, stage_tables)
+int mh_scene_update_emitter(mh_scene *s, uint32_t emitter, const float radiance[3]) {
+    if (!s || !radiance) return set_error(MH_ERR_INVALID_ARGUMENT, "mh_scene_update_emitter: NULL argument");
+    if (emitter >= s->h_emitters.size())
+        return set_error(MH_ERR_INVALID_ARGUMENT, "mh_scene_update_emitter: emitter index out of bounds");
+    MH_HIP(hipSetDevice(s->device));
+    memcpy(s->h_emitters[emitter].radiance, radiance, 12);
+    MH_HIP(hipMemcpyAsync(s->emitters.as<DEmitter>() + emitter, &s->h_emitters[emitter], sizeof(DEmitter),
                           hipMemcpyHostToDevice, s->stream));
     MH_HIP(hipStreamSynchronize(s->stream));
     return MH_OK;
@@ -1247,14 +1263,15 @@ static int prb_weights_impl(mh_scene *s, uint32_t seed, uint32_t spp, uint32_t s
 // ---------------------------------------------------------------------------
 // Differentiated parameters -> slots: small slots 0..n_rgb-1 (register
 // accumulators): rgb textures, medium albedo, homogeneous sigma_t; large
-// slots (global atomics / tangent arrays): bitmaps, grids
+// slots (global atomics / tangent arrays): bitmaps, grids; an emitter's
+// radiance is a small slot too (emitter_slot)
 // ---------------------------------------------------------------------------
 struct Slots {
-    std::vector<int32_t> slot_of_tex, sigma_slot, albedo_slot;
+    std::vector<int32_t> slot_of_tex, sigma_slot, albedo_slot, emitter_slot;
     std::vector<uint32_t> is_rgb;
     std::vector<size_t> counts;
     std::vector<uint32_t> slot_of_param;
-    uint32_t n_rgb = 0, n_bmp = 0, n_medium_params = 0, bmp_tex = 0;
+    uint32_t n_rgb = 0, n_bmp = 0, n_medium_params = 0, n_emitter_params = 0, bmp_tex = 0;
     uint32_t grid_res[kMaxParams][3] = {};  // large sigma_t slots: the grid's resolution (x, y, z)
     std::vector<float *> corner;            // their corner blocks (upload_slots, corners = true)
     bool fx = false;                        // the blocks hold int64 fixed point (deterministic)
@@ -1267,6 +1284,7 @@ static int build_slots(const mh_scene *s, uint32_t n_params, const uint32_t *par
     P.slot_of_tex.assign(std::max<uint32_t>(s->n_textures, 1), -1);
     P.sigma_slot.assign(std::max<uint32_t>(s->n_media, 1), -1);
     P.albedo_slot = P.sigma_slot;
+    P.emitter_slot.assign(std::max<size_t>(s->h_emitters.size(), 1), -1);
     P.is_rgb.assign(kMaxParams, 0);
     P.counts.assign(kMaxParams, 0);
     P.slot_of_param.assign(n_params, 0);
@@ -1294,6 +1312,10 @@ static int build_slots(const mh_scene *s, uint32_t n_params, const uint32_t *par
                 small = md.type == MH_MEDIUM_HOMOGENEOUS;
                 cnt = small ? 1 : (size_t)md.grid_res[0] * md.grid_res[1] * md.grid_res[2];
             }
+        } else if (kind == MH_PARAM_EMITTER_RADIANCE) {
+            if (idx >= s->h_emitters.size()) return set_error(MH_ERR_INVALID_ARGUMENT, a + ": emitter index out of bounds");
+            ++P.n_emitter_params;
+            owner = &P.emitter_slot[idx]; small = true; cnt = 3;
         } else {
             return set_error(MH_ERR_INVALID_ARGUMENT, a + ": unknown parameter kind");
         }
@@ -1318,7 +1340,7 @@ static int build_slots(const mh_scene *s, uint32_t n_params, const uint32_t *par
 }
 
 // per-slot device buffers (s->tmp_c, zeroed) and the meta block
-// slot_of_tex | is_rgb | bufs | sigma_slot | albedo_slot (s->grad_meta)
+// slot_of_tex | is_rgb | bufs | sigma_slot | albedo_slot | corner | emitter_slot (s->grad_meta)
 // corners: the grid sigma_t slots scatter into per-cell corner blocks
 // (s->grid_corner, zeroed; launch_corner_gather after the backward) unless
 // MH_GRID_CORNER=0, the block would exceed 16 GiB or cannot be allocated
@@ -1363,7 +1385,8 @@ static hipError_t upload_slots(mh_scene *s, Slots &P, hipStream_t st, std::vecto
     auto al16 = [](size_t x) { return (x + 15) / 16 * 16; };
     const size_t o_slot = 0, o_isrgb = al16(P.slot_of_tex.size() * 4), o_bufs = al16(o_isrgb + kMaxParams * 4),
                  o_sig = al16(o_bufs + kMaxParams * 8), o_alb = al16(o_sig + P.sigma_slot.size() * 4),
-                 o_cor = al16(o_alb + P.albedo_slot.size() * 4), meta_bytes = al16(o_cor + kMaxParams * 8);
+                 o_cor = al16(o_alb + P.albedo_slot.size() * 4), o_em = al16(o_cor + kMaxParams * 8),
+                 meta_bytes = al16(o_em + P.emitter_slot.size() * 4);
     std::vector<uint8_t> &meta = P.meta;
     meta.assign(meta_bytes, 0);
     memcpy(meta.data() + o_slot, P.slot_of_tex.data(), P.slot_of_tex.size() * 4);
@@ -1372,6 +1395,7 @@ static hipError_t upload_slots(mh_scene *s, Slots &P, hipStream_t st, std::vecto
     memcpy(meta.data() + o_sig, P.sigma_slot.data(), P.sigma_slot.size() * 4);
     memcpy(meta.data() + o_alb, P.albedo_slot.data(), P.albedo_slot.size() * 4);
     memcpy(meta.data() + o_cor, P.corner.data(), kMaxParams * 8);
+    memcpy(meta.data() + o_em, P.emitter_slot.data(), P.emitter_slot.size() * 4);
     // uploaded only when it changes (a new parameter set or reallocated slot
     // buffers), then with a stream sync; repeated calls with the same
     // parameters stay asynchronous
@@ -1391,6 +1415,7 @@ static hipError_t upload_slots(mh_scene *s, Slots &P, hipStream_t st, std::vecto
     ga.n_rgb = P.n_rgb;
     ga.sigma_slot = P.n_medium_params ? reinterpret_cast<const int32_t *>(mb + o_sig) : nullptr;
     ga.albedo_slot = P.n_medium_params ? reinterpret_cast<const int32_t *>(mb + o_alb) : nullptr;
+    ga.emitter_off = P.n_emitter_params ? (uint32_t)(o_em - o_slot) : 0u;
     bool any_corner = false;
     for (float *c : P.corner) any_corner = any_corner || c;
     ga.corner = any_corner ? reinterpret_cast<float *const *>(mb + o_cor) : nullptr;
@@ -1696,7 +1721,7 @@ static int render_backward_impl(mh_scene *s, const mh_integrator *in, uint32_t s
                                         s->wf_ctr.as<uint32_t>() + ctr_per_chunk * chunk, n_bounces, grid,
                                         (odd ? s->wf_partial2 : s->wf_partial).as<float>(), odd ? s->stream2 : st,
                                         &s->evpool[3 * chunk], bmp_wf ? &bc : nullptr,
-                                        det_grad ? s->wf_ws_det.ptr : nullptr));
+                                        det_grad ? s->wf_ws_det.ptr : nullptr, ga.emitter_off));
         }
         if (two) MH_HIP(join_stream(s, st));
         MH_HIP(launch_wf_grad_reduce(s->wf_partial.as<float>(), grid, n_rgb, ga.bufs, st));
@@ -1981,7 +2006,8 @@ static int render_forward_impl(mh_scene *s, const mh_integrator *in, uint32_t se
         if (wavefront)
             MH_HIP(launch_wavefront_fwd(s->S, *in, lm, seed_value, n, ga.slot_of_tex, ga.bufs, ga.is_rgb,
                                         s->work.as<float>(), plane, alpha, s->wf_ws.ptr, s->wf_ws_prb.ptr, plane,
-                                        s->wf_ctr.as<uint32_t>(), in->max_depth, wf_grid(wf_blocks(cus)), st));
+                                        s->wf_ctr.as<uint32_t>(), in->max_depth, wf_grid(wf_blocks(cus)), st,
+                                        ga.emitter_off));
         else
             MH_HIP(launch_render_forward(s->S, *in, lm, seed_value, n, plane, s->work.as<float>(), ga,
                                          s->counters.as<unsigned long long>(), st, alpha));

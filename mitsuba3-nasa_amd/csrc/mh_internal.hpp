@@ -28,7 +28,13 @@ struct GradArgs {
     float *const *bufs;          // device: slot -> gradient buffer
     const uint32_t *is_rgb;      // device: slot -> 1 if rgb
     uint32_t n_rgb;              // small (register-accumulated) slots are 0 .. n_rgb-1:
-                                 // rgb textures, medium albedo, homogeneous sigma_t
+                                 // rgb textures, medium albedo, homogeneous sigma_t, emitter radiance
+    // the emitter -> radiance slot (or -1) table, as its byte offset from
+    // slot_of_tex (both lie in one meta block); 0 when no emitter parameter is
+    // listed, which selects the kernel instances without the emitter terms.
+    // (An offset in the struct's padding rather than a pointer: the kernel
+    // arguments of those instances keep their layout.)
+    uint32_t emitter_off = 0;
     const int32_t *sigma_slot;   // device: medium -> sigma_t slot or -1 (prbvolpath)
     const int32_t *albedo_slot;  // device: medium -> albedo slot or -1 (prbvolpath)
     int32_t lds_slot = -1;       // bitmap slot accumulated per workgroup in LDS (k_prb_backward replay)
@@ -55,6 +61,10 @@ struct GradArgs {
     float *hot_buf = nullptr;    // bufs[hot_sigma]
     float *hot_corner = nullptr; // corner[hot_sigma] (nullptr: atomics into hot_buf)
 };
+__host__ __device__ inline const int32_t *emitter_slot_table(const int32_t *slot_of_tex, uint32_t emitter_off) {
+    return emitter_off ? reinterpret_cast<const int32_t *>(reinterpret_cast<const uint8_t *>(slot_of_tex) + emitter_off)
+                       : nullptr;
+}
 
 // ---- BVH builder (host, binned SAH) --------------------------------------
 struct BuildPrim {
@@ -140,7 +150,8 @@ hipError_t launch_wavefront_prb(const DScene &S, const IntegratorParams &in, con
                                 uint32_t grid, float *partial, hipStream_t st,
                                 hipEvent_t *span = nullptr,               // span: 2 events around the bounce launches
                                 const WfBitmapArgs *bmp = nullptr,       // the bitmap parameters (or none)
-                                void *ws_det = nullptr);                 // deterministic rgb gradients (or none)
+                                void *ws_det = nullptr,                  // deterministic rgb gradients (or none)
+                                uint32_t emitter_off = 0);               // GradArgs::emitter_off (0: no emitter parameter)
 size_t wf_det_workspace_bytes(uint64_t cap);
 // render_forward of `prb` on the fused wavefront (packet-engine scenes): the
 // tangent radiance of every path written to the sample planes of launch_render
@@ -148,7 +159,7 @@ hipError_t launch_wavefront_fwd(const DScene &S, const IntegratorParams &in, con
                                 uint64_t n, const int32_t *slot_of_tex, float *const *tangents,
                                 const uint32_t *is_rgb, float *out, uint64_t plane, int alpha, void *ws,
                                 void *ws_prb, uint64_t cap, uint32_t *ctr, uint32_t n_bounces, uint32_t grid,
-                                hipStream_t st);
+                                hipStream_t st, uint32_t emitter_off = 0);  // GradArgs::emitter_off
 hipError_t launch_wf_grad_reduce(const float *partial, uint32_t grid, uint32_t n_rgb, float *const *bufs,
                                  hipStream_t st);
 // max of a float array (gridvolume max for the majorant), as an order-preserving

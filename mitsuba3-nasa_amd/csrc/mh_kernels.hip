@@ -774,7 +774,9 @@ k_render_forward(DScene S, IntegratorParams in, LaneMap lm, uint32_t seed_value,
 #ifndef MH_PRB_WAVES
 #define MH_PRB_WAVES 4  // replay backward: 128 VGPRs (4 waves/SIMD, ~28 spilled) measured faster than 3 waves
 #endif
-template <bool InLds, bool Fused>
+// Em: the call lists an emitter's radiance (GradArgs::emitter_off); the
+// instances without it are the kernels of a call that lists none
+template <bool InLds, bool Fused, bool Em = false>
 __global__ void __launch_bounds__(256, Fused ? 1 : MH_PRB_WAVES)
 k_prb_backward(DScene S, IntegratorParams in, LaneMap lm, uint32_t seed_value, uint64_t n,
                int coalesce, const float *__restrict__ grad_in, const float *__restrict__ weights,
@@ -806,12 +808,12 @@ k_prb_backward(DScene S, IntegratorParams in, LaneMap lm, uint32_t seed_value, u
                             __builtin_fmaf(sy, S.inv_height, -0.f));
         V3 dL = gather_dL_wave(S, coalesce, grad_in, sx, sy);  // grad_in: pre-divided by W (k_grad_over_w)
         if (Fused) {
-            prb_fused(S, B, in, rng, r, dL, ga.n_rgb, g, n_closest, n_shadow);
+            prb_fused<Em>(S, B, in, rng, r, dL, ga.n_rgb, g, n_closest, n_shadow);
         } else {
             Pcg rng_primal = rng;  // sampler.clone()
             V3 Lp = prb_sample<false>(S, B, in, rng_primal, r, v3(0, 0, 0), v3(0, 0, 0), nullptr,
                                       n_closest, n_shadow);
-            prb_sample<true>(S, B, in, rng, r, dL, Lp, &g, n_closest, n_shadow);
+            prb_sample<true, Em>(S, B, in, rng, r, dL, Lp, &g, n_closest, n_shadow);
         }
     }
     if (tex_acc) {
@@ -1264,8 +1266,9 @@ hipError_t launch_prb_backward(const DScene &S, const IntegratorParams &in, cons
         // the kernel's static LDS (GradCtx's per-wave fixed-point sums,
         // g_fx_wave) comes on top of the dynamic bytes
         hipFuncAttributes fa{};
-        const void *fn = S.lds_bytes_bvh ? (fused ? (const void *)k_prb_backward<true, true> : (const void *)k_prb_backward<true, false>)
-                                         : (fused ? (const void *)k_prb_backward<false, true> : (const void *)k_prb_backward<false, false>);
+        const bool em = ga.emitter_off != 0;  // (fused is false here)
+        const void *fn = S.lds_bytes_bvh ? (em ? (const void *)k_prb_backward<true, false, true> : (const void *)k_prb_backward<true, false>)
+                                         : (em ? (const void *)k_prb_backward<false, false, true> : (const void *)k_prb_backward<false, false>);
         const size_t st_lds = hipFuncGetAttributes(&fa, fn) == hipSuccess ? fa.sharedSizeBytes : (size_t)kFxStaticLdsBytes;
         const uint32_t off = (uint32_t)((sh + 15) / 16 * 16);
         const size_t total = off + (size_t)ga.lds_floats * 4;
@@ -1293,14 +1296,22 @@ hipError_t launch_prb_backward(const DScene &S, const IntegratorParams &in, cons
             hipLaunchKernelGGL((k_prbvol_backward<true>), g, b, sh, st, S, in, lm, seed_value, n, coalesce, grad_in, ga, counters, wk);
         else
             hipLaunchKernelGGL((k_prbvol_backward<false>), g, b, sh, st, S, in, lm, seed_value, n, coalesce, grad_in, ga, counters, wk);
-    } else if (S.lds_bytes_bvh && fused)
-        hipLaunchKernelGGL((k_prb_backward<true, true>), g, b, sh, st, S, in, lm, seed_value, n, coalesce, grad_in, weights, ga, counters);
-    else if (S.lds_bytes_bvh)
-        hipLaunchKernelGGL((k_prb_backward<true, false>), g, b, sh, st, S, in, lm, seed_value, n, coalesce, grad_in, weights, ga, counters);
-    else if (fused)
-        hipLaunchKernelGGL((k_prb_backward<false, true>), g, b, sh, st, S, in, lm, seed_value, n, coalesce, grad_in, weights, ga, counters);
-    else
-        hipLaunchKernelGGL((k_prb_backward<false, false>), g, b, sh, st, S, in, lm, seed_value, n, coalesce, grad_in, weights, ga, counters);
+    } else {
+#define MH_PRB_BACKWARD(LDS, FUSED, EM)                                                                          \
+    hipLaunchKernelGGL((k_prb_backward<LDS, FUSED, EM>), g, b, sh, st, S, in, lm, seed_value, n, coalesce, grad_in, \
+                       weights, ga, counters)
+#define MH_PRB_BACKWARD_EM(LDS, FUSED)                                                                           \
+    do {                                                                                                         \
+        if (ga.emitter_off) MH_PRB_BACKWARD(LDS, FUSED, true);                                                   \
+        else MH_PRB_BACKWARD(LDS, FUSED, false);                                                                 \
+    } while (0)
+        if (S.lds_bytes_bvh && fused) MH_PRB_BACKWARD_EM(true, true);
+        else if (S.lds_bytes_bvh) MH_PRB_BACKWARD_EM(true, false);
+        else if (fused) MH_PRB_BACKWARD_EM(false, true);
+        else MH_PRB_BACKWARD_EM(false, false);
+#undef MH_PRB_BACKWARD_EM
+#undef MH_PRB_BACKWARD
+    }
     return hipGetLastError();
 }
 

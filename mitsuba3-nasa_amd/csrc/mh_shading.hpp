@@ -1540,6 +1540,54 @@ MH_DEV V3 sample_emitter_direction(const DScene &S, const LdsBvh &B, const SI &s
     return spec;
 }
 
+// ---- an emitter's radiance as a differentiable parameter --------------------
+// The radiance of emitter e enters a sample linearly: through emitter_eval at
+// a direct hit, and through the weight of an emitter sample.  The derivative
+// factors below never divide by the radiance (which may be zero).
+// emitter_eval / radiance: the emitter's geometric mask
+MH_DEV float emitter_eval_mask(const DScene &S, uint32_t em, const SI &si) {
+    const uint32_t type = S.emitters[em].type;
+    if (type == MH_EMITTER_AREA) return si.wi.z > 0.f ? 1.f : 0.f;
+    return type == MH_EMITTER_CONSTANT ? 1.f : 0.f;
+}
+// the emitter scene_sample_emitter_direction picked for the sample sx
+MH_DEV uint32_t sampled_emitter(const DScene &S, float sx) {
+    const uint32_t n = S.n_emitters;
+    if (n <= 1) return 0u;
+    const uint32_t idx = (uint32_t)(sx * S.n_emitters_f);
+    return idx > n - 1 ? n - 1 : idx;
+}
+// d(weight) / d(radiance) of that sample before the visibility test: 1 / pdf
+// (ds.pdf holds the emitter choice's 1 / n), zero where the emitter masks its
+// own sample (an area light seen from behind) or the sample failed
+MH_DEV float emitter_sample_inv_pdf(const DScene &S, uint32_t em, const DirS &ds) {
+    if (ds.pdf == 0.f) return 0.f;
+    if (S.emitters[em].type == MH_EMITTER_AREA && !(dot(ds.d, ds.n) < 0.f)) return 0.f;
+    return rcp(ds.pdf);
+}
+// sample_emitter_direction for a call that differentiates emitters: also the
+// picked emitter's slot (or -1) and the visibility-masked 1 / pdf.  A sample
+// of zero weight still traces its shadow ray when its emitter has a slot.
+MH_DEV V3 sample_emitter_direction_em(const DScene &S, const LdsBvh &B, const SI &si, float sx, float sy, DirS &ds,
+                                      uint32_t &n_shadow, const int32_t *emitter_slot, int32_t &eslot,
+                                      float &inv_pdf) {
+    V3 spec = scene_sample_emitter_direction(S, si.p, sx, sy, ds);
+    const uint32_t e = sampled_emitter(S, sx);
+    eslot = S.n_emitters ? emitter_slot[e] : -1;
+    inv_pdf = eslot >= 0 ? emitter_sample_inv_pdf(S, e, ds) : 0.f;
+    if (ds.pdf != 0.f && (nonzero(spec) || inv_pdf != 0.f)) {
+        RayT r = spawn_ray_to(si.p, si.n, ds.p);
+        Hit h;
+        ++n_shadow;
+        if (traverse<true>(B.nodes, B.prims, B.stack, B.stride, r, h)) {
+            spec = v3(0, 0, 0);
+            ds.pdf = 0.f;
+            inv_pdf = 0.f;
+        }
+    }
+    return spec;
+}
+
 // PerspectiveCamera::sample_ray_differential (sensors/perspective.cpp:240-281)
 MH_DEV RayT camera_ray(const DScene &S, float ax, float ay) {
     const float *m = S.sample_to_camera;
@@ -1715,6 +1763,8 @@ struct GradCtx {
     float fsum;
     int32_t hot_med, hot_sigma, hot_albedo;  // GradArgs::hot_* (the first medium with a parameter)
     float *hot_buf, *hot_corner;
+    const int32_t *emitter_slot;  // emitter -> slot of its radiance or -1 (nullptr: none).  Read by the Em instances,
+                                  // and at run time by prb_forward and prbvol_sample (the per-sample kernels)
 };
 
 // register accumulator of a small (rgb / scalar) parameter slot
@@ -1773,6 +1823,19 @@ MH_DEV void acc_add(GradCtx &g, int32_t k, V3 a) {
 }
 MH_DEV V3 acc_get(const GradCtx &g, int32_t k) {
     return k == 0 ? g.acc0 : k == 1 ? g.acc1 : k == 2 ? g.acc2 : k == 3 ? g.acc3 : v3(0.f, 0.f, 0.f);
+}
+
+// input tangent of an emitter's radiance (forward mode: bufs hold the tangents)
+MH_DEV V3 emitter_tangent(const GradCtx &g, int32_t k) {
+    if (k < 0) return v3(0.f, 0.f, 0.f);
+    const float *t = g.bufs[k];
+    return v3(t[0], t[1], t[2]);
+}
+// adjoint of an emitter's radiance (a small slot); forward mode: <adj, tangent>
+MH_DEV void emitter_backward(int32_t k, V3 adj, GradCtx &g) {
+    if (k < 0) return;
+    if (g.fwd) g.fsum += (adj.x * g.bufs[k][0] + adj.y * g.bufs[k][1]) + adj.z * g.bufs[k][2];
+    else acc_add(g, k, adj);
 }
 
 // ---------------------------------------------------------------------------
@@ -1912,7 +1975,10 @@ MH_DEV void tex_backward(const DScene &S, uint32_t tex, float uvx, float uvy, V3
     }
 }
 
-template <bool Grad>
+// Em: an emitter's radiance is differentiated (GradCtx::emitter_slot): the
+// adjoints of prb.py:135 (Le = beta mis eval(si)) and prb.py:156-163 (the
+// emitter sample's radiance / pdf), both linear in the radiance
+template <bool Grad, bool Em = false>
 MH_DEV V3 prb_sample(const DScene &S, const LdsBvh &B, const IntegratorParams &in, Pcg &rng,
                      RayT ray, V3 dL, V3 L, GradCtx *g, uint32_t &n_closest, uint32_t &n_shadow,
                      bool *valid_out = nullptr) {
@@ -1945,6 +2011,9 @@ MH_DEV V3 prb_sample(const DScene &S, const LdsBvh &B, const IntegratorParams &i
             if (active_next)
                 le = emitter_eval(S, em, si);
             Le = (beta * mis) * le;
+            if constexpr (Grad && Em) {
+                if (active_next) emitter_backward(g->emitter_slot[em], (dL * (beta * mis)) * emitter_eval_mask(S, em, si), *g);
+            }
         }
 
         // ---- emitter sampling (prb.py:139-163)
@@ -1956,8 +2025,13 @@ MH_DEV V3 prb_sample(const DScene &S, const LdsBvh &B, const IntegratorParams &i
         ds.d = v3(0, 0, 0);
         ds.delta = false;
         V3 em_weight = v3(0, 0, 0);
+        int32_t em_slot = -1;   // Em: the sampled emitter's slot and d em_weight / d radiance
+        float em_inv_pdf = 0.f;
         if (active_em) {
-            em_weight = sample_emitter_direction(S, B, si, e0, e1, ds, n_shadow);
+            if constexpr (Grad && Em)
+                em_weight = sample_emitter_direction_em(S, B, si, e0, e1, ds, n_shadow, g->emitter_slot, em_slot, em_inv_pdf);
+            else
+                em_weight = sample_emitter_direction(S, B, si, e0, e1, ds, n_shadow);
             active_em = ds.pdf != 0.f;
         }
         V3 rho = v3(0, 0, 0);
@@ -1969,6 +2043,9 @@ MH_DEV V3 prb_sample(const DScene &S, const LdsBvh &B, const IntegratorParams &i
         float mis_em = ds.delta ? 1.f : mis_weight(ds.pdf, bsdf_pdf_em);
         V3 beta_mis_em = beta * mis_em;
         V3 Lr_dir = active_em ? (beta_mis_em * bsdf_value_em) * em_weight : v3(0, 0, 0);
+        if constexpr (Grad && Em) {
+            if (active_em) emitter_backward(em_slot, (dL * (beta_mis_em * bsdf_value_em)) * em_inv_pdf, *g);
+        }
 
         // ---- detached BSDF sampling (prb.py:167-170)
         (void)rng.next_float();
@@ -2301,6 +2378,7 @@ MH_DEV void add_slot(float (&arr)[NR][3], int32_t slot, V3 v) {
     }
 }
 
+template <bool Em = false>
 MH_DEV void prb_fused(const DScene &S, const LdsBvh &B, const IntegratorParams &in, Pcg &rng,
                       RayT ray, V3 dL, uint32_t n_rgb, GradCtx &g, uint32_t &n_closest, uint32_t &n_shadow) {
     uint32_t depth = 0;
@@ -2339,6 +2417,9 @@ MH_DEV void prb_fused(const DScene &S, const LdsBvh &B, const IntegratorParams &
             if (active_next)
                 le = emitter_eval(S, em, si);
             charge(acc, A, n_rgb, dL * ((beta * mis) * le));
+            if constexpr (Em) {  // d Le / d radiance (prb.py:135)
+                if (active_next) add_slot(acc, g.emitter_slot[em], (dL * (beta * mis)) * emitter_eval_mask(S, em, si));
+            }
         }
         active_next = active_next && (depth + 1 < in.max_depth) && si.valid;
         bool active_em = active_next && smooth;
@@ -2348,8 +2429,13 @@ MH_DEV void prb_fused(const DScene &S, const LdsBvh &B, const IntegratorParams &
         ds.d = v3(0, 0, 0);
         ds.delta = false;
         V3 em_weight = v3(0, 0, 0);
+        int32_t em_slot = -1;   // Em: the sampled emitter's slot and d em_weight / d radiance
+        float em_inv_pdf = 0.f;
         if (active_em) {
-            em_weight = sample_emitter_direction(S, B, si, e0, e1, ds, n_shadow);
+            if constexpr (Em)
+                em_weight = sample_emitter_direction_em(S, B, si, e0, e1, ds, n_shadow, g.emitter_slot, em_slot, em_inv_pdf);
+            else
+                em_weight = sample_emitter_direction(S, B, si, e0, e1, ds, n_shadow);
             active_em = ds.pdf != 0.f;
         }
         V3 rho = v3(0, 0, 0);
@@ -2361,6 +2447,9 @@ MH_DEV void prb_fused(const DScene &S, const LdsBvh &B, const IntegratorParams &
         float mis_em = ds.delta ? 1.f : mis_weight(ds.pdf, bsdf_pdf_em);
         V3 beta_mis_em = beta * mis_em;
         if (active_em) charge(acc, A, n_rgb, dL * ((beta_mis_em * bsdf_value_em) * em_weight));
+        if constexpr (Em) {  // d Lr_dir / d radiance (prb.py:156-163)
+            if (active_em) add_slot(acc, em_slot, (dL * (beta_mis_em * bsdf_value_em)) * em_inv_pdf);
+        }
         (void)rng.next_float();
         float s2x = rng.next_float(), s2y = rng.next_float();
         V3 bs_wo = v3(0, 0, 0), bsdf_weight = v3(0, 0, 0);
@@ -2438,6 +2527,8 @@ MH_DEV V3 prb_forward(const DScene &S, const LdsBvh &B, const IntegratorParams &
             if (active_next)
                 le = emitter_eval(S, em, si);
             dL = dL + ((beta * mis) * le) * (T * kInvPi);
+            if (g.emitter_slot && active_next)  // the radiance's own tangent (prb.py:135)
+                dL = dL + ((beta * mis) * emitter_eval_mask(S, em, si)) * emitter_tangent(g, g.emitter_slot[em]);
         }
         active_next = active_next && (depth + 1 < in.max_depth) && si.valid;
         bool active_em = active_next && smooth;
@@ -2447,8 +2538,13 @@ MH_DEV V3 prb_forward(const DScene &S, const LdsBvh &B, const IntegratorParams &
         ds.d = v3(0, 0, 0);
         ds.delta = false;
         V3 em_weight = v3(0, 0, 0);
+        int32_t em_slot = -1;   // the sampled emitter's slot and d em_weight / d radiance
+        float em_inv_pdf = 0.f;
         if (active_em) {
-            em_weight = sample_emitter_direction(S, B, si, e0, e1, ds, n_shadow);
+            if (g.emitter_slot)
+                em_weight = sample_emitter_direction_em(S, B, si, e0, e1, ds, n_shadow, g.emitter_slot, em_slot, em_inv_pdf);
+            else
+                em_weight = sample_emitter_direction(S, B, si, e0, e1, ds, n_shadow);
             active_em = ds.pdf != 0.f;
         }
         V3 rho = v3(0, 0, 0);
@@ -2460,6 +2556,8 @@ MH_DEV V3 prb_forward(const DScene &S, const LdsBvh &B, const IntegratorParams &
         float mis_em = ds.delta ? 1.f : mis_weight(ds.pdf, bsdf_pdf_em);
         V3 beta_mis_em = beta * mis_em;
         if (active_em) dL = dL + ((beta_mis_em * bsdf_value_em) * em_weight) * (T * kInvPi);
+        if (active_em && em_slot >= 0)  // the sampled radiance's tangent (prb.py:156-163)
+            dL = dL + ((beta_mis_em * bsdf_value_em) * em_inv_pdf) * emitter_tangent(g, em_slot);
         (void)rng.next_float();
         float s2x = rng.next_float(), s2y = rng.next_float();
         V3 bs_wo = v3(0, 0, 0), bsdf_weight = v3(0, 0, 0);
@@ -3178,8 +3276,11 @@ struct NeeLog {
 template <int Mode>
 MH_DEV V3 pvp_sample_emitter(const DScene &S, const LdsBvh &B, const MEI &mei_ref, const SI &si_ref,
                              bool active_medium, Pcg &rng, uint32_t medium, DirS &ds, V3 adj_emitted, V3 dL,
-                             GradCtx *g, uint32_t &n_shadow, NeeLog *nl = nullptr) {
+                             GradCtx *g, uint32_t &n_shadow, NeeLog *nl = nullptr, V3 *tr_out = nullptr) {
+    // tr_out: the walk's transmittance on its own (the emitter's radiance is
+    // differentiated: emitter_val may be zero, so the product does not give it)
     constexpr bool Adj = Mode == 1;
+    if (tr_out) *tr_out = v3(0.f, 0.f, 0.f);
     if (Mode == 2) { nl->n = 0; nl->overflow = false; }
     const V3 ref_p = active_medium ? mei_ref.p : si_ref.p;
     const V3 ref_n = active_medium ? v3(0.f, 0.f, 0.f) : si_ref.n;
@@ -3265,6 +3366,7 @@ MH_DEV V3 pvp_sample_emitter(const DScene &S, const LdsBvh &B, const MEI &mei_re
         if (active) total_dist += act_med ? mei.t : si_t;
         if (act_surf && is_medium_transition(S, si)) medium = target_medium(S, si, ray.d);
     }
+    if (tr_out) *tr_out = transmittance;
     return emitter_val * transmittance;
 }
 
@@ -3487,10 +3589,14 @@ MH_DEV V3 prbvol_sample(const DScene &S, const LdsBvh &B, const IntegratorParams
             const Pcg nee_rng = rng;   // sampler.clone()
             DirS ds;
             const bool logged = NeeGrad && nl;
+            V3 tr_nee = v3(0.f, 0.f, 0.f);  // the walk's transmittance (an emitter parameter's adjoint)
+            V3 *tr_out = (NeeGrad && g->emitter_slot) ? &tr_nee : nullptr;
             const V3 emitted = logged ? pvp_sample_emitter<2>(S, B, mei, si, active_e_medium, rng, medium, ds,
-                                                              v3(0.f, 0.f, 0.f), v3(0.f, 0.f, 0.f), nullptr, n_shadow, nl)
+                                                              v3(0.f, 0.f, 0.f), v3(0.f, 0.f, 0.f), nullptr, n_shadow, nl,
+                                                              tr_out)
                                       : pvp_sample_emitter<0>(S, B, mei, si, active_e_medium, rng, medium, ds,
-                                                              v3(0.f, 0.f, 0.f), v3(0.f, 0.f, 0.f), nullptr, n_shadow);
+                                                              v3(0.f, 0.f, 0.f), v3(0.f, 0.f, 0.f), nullptr, n_shadow,
+                                                              nullptr, tr_out);
             V3 nee_w, bv = v3(0.f, 0.f, 0.f);
             float nee_pdf, bp = 0.f;
             const V3 wo_s = to_local(si, ds.d);
@@ -3508,6 +3614,14 @@ MH_DEV V3 prbvol_sample(const DScene &S, const LdsBvh &B, const IntegratorParams
             const V3 contrib = ((throughput * nee_w) * mis) * emitted;
             L = Adj ? L + (-contrib) : L + contrib;
             if (NeeGrad) {
+                if (g->emitter_slot && S.n_emitters) {
+                    // backward(dL * contrib) through the sampled emitter's radiance (prbvolpath.py:346-351:
+                    // emitter_val = radiance / pdf), the only place it enters prbvolpath's sample
+                    Pcg er = nee_rng;
+                    const uint32_t e = sampled_emitter(S, er.next_float());
+                    const V3 base = (throughput * nee_w) * mis;
+                    emitter_backward(g->emitter_slot[e], ((dL * base) * tr_nee) * emitter_sample_inv_pdf(S, e, ds), *g);
+                }
                 if (logged && !nl->overflow) {  // the logged walk's steps: coef * (dL . adj_emitted)
                     const float K = (dL.x * contrib.x + dL.y * contrib.y) + dL.z * contrib.z;
                     charge_walk_log(S, nl->buf + nl->t, nl->stride, nl->n, nl->med, K, *g);
@@ -3690,6 +3804,7 @@ MH_DEV GradCtx make_grad_ctx(const GradArgs &ga) {
     g.hot_albedo = ga.hot_albedo;
     g.hot_buf = ga.hot_buf;
     g.hot_corner = ga.hot_corner;
+    g.emitter_slot = emitter_slot_table(ga.slot_of_tex, ga.emitter_off);
     return g;
 }
 

@@ -817,6 +817,7 @@ struct PvNoHook {
     template <class V> MH_DEV void walk_step(V &, V3, float) {}
     template <class V>
     MH_DEV void nee_charge(const DScene &, const LdsBvh &, V &, const Pcg &, V3, V3, float, V3, uint32_t &) {}
+    template <class V> MH_DEV void nee_emitter(const DScene &, V &, const Pcg &, V3) {}
     template <class V> MH_DEV void surface_log(const DScene &, V &, V3) {}
 };
 
@@ -1098,6 +1099,7 @@ MH_DEV uint32_t pv_post(const DScene &S, const LdsBvh &B, const IntegratorParams
         const V3 contrib = ((v.throughput * nee_w) * mis) * emitted;
         v.L = v.L + contrib;
         hk.nee_charge(S, B, v, rng, contrib, emitted, mis, wo_s, n_shadow);
+        hk.nee_emitter(S, v, rng, (v.throughput * nee_w) * mis);  // contrib / emitted (used by PvBwdMachineEm only)
     }
     v.valid_ray = v.valid_ray || v.act_scatter;
     bool act_scatter = v.act_scatter;
@@ -1442,6 +1444,7 @@ struct PvBwdMachine {
             tex_backward(S, S.bsdf_tex[S.shapes[v.si.shape].bsdf], v.si.uvx, v.si.uvy, adj, g);
         }
     }
+    MH_DEV void nee_emitter(const DScene &, State &, const Pcg &, V3) {}  // PvBwdMachineEm's hook
     // Lo = bsdf_eval * detach(L / max(1e-8, bsdf_eval)) (prbvolpath.py:305-312), logged
     MH_DEV void surface_log(const DScene &S, State &v, V3 bs_wo) {
         const V3 be = (v.rho * kInvPi) * bs_wo.z;
@@ -1893,6 +1896,31 @@ hipError_t launch_vol_sched(const DScene &S, const IntegratorParams &in, const L
     return hipGetLastError();
 }
 
+// PvBwdMachine for a call that lists an emitter's radiance
+// (GradArgs::emitter_off): the emitter sample's contribution is linear in the
+// sampled emitter's radiance (prbvolpath.py:346-351, the only place it enters
+// prbvolpath's sample), so POST also charges dL base transmittance / pdf to
+// that emitter's slot -- through acc_add, hence in fixed point under
+// MH_FLAG_DETERMINISTIC.  The sampled emitter is recovered from the sampler
+// state kept for the walk's replay (nee_state).  A machine of its own, so that
+// k_vol_sched<PvBwdMachine> stays the kernel of a call without emitters.
+struct PvBwdMachineEm : PvBwdMachine {
+    using PvBwdMachine::PvBwdMachine;
+    MH_DEV void nee_emitter(const DScene &S, State &v, const Pcg &rng, V3 base) {
+        if (!S.n_emitters) return;
+        Pcg er;
+        er.state = v.nee_state;
+        er.inc = rng.inc;
+        const uint32_t e = sampled_emitter(S, er.next_float());
+        const int32_t k = g.emitter_slot[e];
+        if (k >= 0) acc_add(g, k, ((v.dL * base) * v.transmittance) * emitter_sample_inv_pdf(S, e, v.ds));
+    }
+    MH_DEV uint32_t post(const DScene &S, const LdsBvh &B, const IntegratorParams &in, Pcg &rng, State &v,
+                         uint32_t &ns) {
+        return pv_post(S, B, in, rng, v, *this, ns);
+    }
+};
+
 #ifdef MH_EXP_VSCNT
 extern "C" int mh_exp_vs_sub(unsigned long long *out, int reset) {
     hipMemcpyFromSymbol(out, HIP_SYMBOL(g_vs_sub), sizeof(g_vs_sub));
@@ -1920,14 +1948,20 @@ hipError_t launch_vol_sched_bwd(const DScene &S, const IntegratorParams &in, con
     unsigned long long *work = counters + 32;  // the 8 queue heads of this launch (128 B apart)
     hipError_t e = hipMemsetAsync(work, 0, 8 * 128, st);
     if (e != hipSuccess) return e;
-#define MH_VSB(L, P, T)                                                                                        \
-    hipLaunchKernelGGL((k_vol_sched<PvBwdMachine, L, P, T>), dim3(grid), dim3(256), sh + (T ? vs_tab_bytes(S) : 0u) + (P ? vs_defer_bytes(S) : 0u), \
+#define MH_VSB1(M, L, P, T)                                                                                    \
+    hipLaunchKernelGGL((k_vol_sched<M, L, P, T>), dim3(grid), dim3(256), sh + (T ? vs_tab_bytes(S) : 0u) + (P ? vs_defer_bytes(S) : 0u), \
                        st, S, in, lm, seed_value, n, (uint64_t)0, (float *)nullptr, counters, work, 0, bw)
+#define MH_VSB(L, P, T)                                                                                        \
+    do {                                                                                                       \
+        if (bw.ga.emitter_off) MH_VSB1(PvBwdMachineEm, L, P, T);                                               \
+        else MH_VSB1(PvBwdMachine, L, P, T);                                                                   \
+    } while (0)
     if (pk && tab) MH_VSB(false, true, true);
     else if (pk) MH_VSB(false, true, false);
     else if (lds) MH_VSB(true, false, false);
     else MH_VSB(false, false, false);
 #undef MH_VSB
+#undef MH_VSB1
     return hipGetLastError();
 }
 

@@ -852,6 +852,10 @@ struct WfPrb {
     float *partial;   // [grid][kG]
     const int32_t *slot_of_tex;
     uint32_t n_rgb;
+    uint32_t emitter_off;  // GradArgs::emitter_off (in the struct's padding; read by the Em instances only)
+    MH_DEV const int32_t *emitter_slot() const {  // emitter -> slot of its radiance or -1
+        return reinterpret_cast<const int32_t *>(reinterpret_cast<const uint8_t *>(slot_of_tex) + emitter_off);
+    }
     // ping-pong k: planes [k * (3 + kG), (k + 1) * (3 + kG)): dL xyz, then A
     MH_DEV float *dl(int k, int c) const { return base + (uint64_t)(k * (3 + kG) + c) * stride; }
     MH_DEV float *A(int k, int c) const { return base + (uint64_t)(k * (3 + kG) + 3 + c) * stride; }
@@ -869,7 +873,8 @@ size_t wf_prb_workspace_bytes(uint64_t cap) {
     return (size_t)(6 + 2 * kG + kG + 2) * align_up(cap * 4);
 }
 
-static WfPrb carve_prb(void *ws, uint64_t cap, float *partial, const int32_t *slot_of_tex, uint32_t n_rgb) {
+static WfPrb carve_prb(void *ws, uint64_t cap, float *partial, const int32_t *slot_of_tex, uint32_t n_rgb,
+                       uint32_t emitter_off = 0) {
     cap = (cap + kSeg - 1) / kSeg * kSeg;
     WfPrb q;
     q.base = reinterpret_cast<float *>(ws);
@@ -877,6 +882,7 @@ static WfPrb carve_prb(void *ws, uint64_t cap, float *partial, const int32_t *sl
     q.partial = partial;
     q.slot_of_tex = slot_of_tex;
     q.n_rgb = n_rgb;
+    q.emitter_off = emitter_off;
     return q;
 }
 
@@ -998,7 +1004,10 @@ k_wf_raygen_prb(DScene S, LaneMap lm, uint32_t seed_value, uint64_t n, int coale
 
 // one iteration of the prb_fused loop (prb.py:114-278) for every queued path
 // NR: rgb slot arrays (1 when a single rgb parameter is differentiated)
-template <bool Staged, int NR>
+// Em: an emitter's radiance is among the small slots (WfPrb::emitter_slot()):
+// its adjoint at a direct hit (prb.py:135) goes to acc, that of an emitter
+// sample (prb.py:156-163) rides in the shadow record G like the other slots'
+template <bool Staged, int NR, bool Em = false>
 __global__ void __launch_bounds__(256, 5)
 k_wf_shade_prb(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value, WfState w, WfPrb q,
                int cur, uint32_t seg_cap, uint32_t *ctr, uint32_t *ctr_next) {
@@ -1062,6 +1071,9 @@ k_wf_shade_prb(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value, 
                 if (active_next)
                     le = emitter_eval(S, em, si);
                 charge(acc, A, n_rgb, dL * ((beta * mis) * le));
+                if constexpr (Em) {
+                    if (active_next) add_slot(acc, q.emitter_slot()[em], (dL * (beta * mis)) * emitter_eval_mask(S, em, si));
+                }
             }
             active_next = active_next && (depth + 1 < in.max_depth) && si.valid;
             const bool active_em0 = active_next && smooth;
@@ -1073,9 +1085,15 @@ k_wf_shade_prb(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value, 
             ds.d = v3(0, 0, 0);
             ds.delta = false;
             V3 em_weight = v3(0, 0, 0);
+            int32_t em_slot = -1;    // Em: the sampled emitter's slot and d em_weight / d radiance
+            float em_inv_pdf = 0.f;
             if (active_em0) {
                 em_weight = scene_sample_emitter_direction(S, si.p, e0, e1, ds);
-                if (ds.pdf != 0.f && nonzero(em_weight)) {
+                if constexpr (Em) {  // a zero-weight sample of a differentiated emitter still needs its visibility
+                    em_slot = S.n_emitters ? q.emitter_slot()[sampled_emitter(S, e0)] : -1;
+                    if (em_slot >= 0) em_inv_pdf = emitter_sample_inv_pdf(S, sampled_emitter(S, e0), ds);
+                }
+                if (ds.pdf != 0.f && (nonzero(em_weight) || (Em && em_inv_pdf != 0.f))) {
                     shadow = true;
                     sray = spawn_ray_to(si.p, si.n, ds.p);
                 }
@@ -1099,6 +1117,7 @@ k_wf_shade_prb(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value, 
                 }
                 if (slot >= 0 && si.wi.z > 0.f && wo_em.z > 0.f)
                     add_slot(G, slot, (((dL * em_weight) * beta_mis_em) * wo_em.z) * kInvPi);
+                if constexpr (Em) add_slot(G, em_slot, (dL * (beta_mis_em * bsdf_value_em)) * em_inv_pdf);
             }
 
             // ---- BSDF sampling, RR (prb.py:181-278)
@@ -1259,7 +1278,9 @@ MH_DEV void nee_ring_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int NR, bool Gen, bool Bm, bool Det>
+// Em: as in k_wf_shade_prb; the emitter-sample adjoint is one more entry of
+// G, so it follows the shadow ray through the NEE ring and into Det's sums
+template <int NR, bool Gen, bool Bm, bool Det, bool Em = false>
 __global__ void __launch_bounds__(256, Bm ? MH_BOUNCE_BMP_WAVES : MH_BOUNCE_PRB_WAVES)
 k_wf_bounce_prb(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value, WfState w, WfPrb q,
                 int cur, uint32_t seg_cap, uint32_t *ctr, uint32_t *ctr_next, PrbGen gen, WfBmp bm, WfDet det) {
@@ -1399,6 +1420,13 @@ k_wf_bounce_prb(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value,
                 if (Det) charge(Pp, A, n_rgb, dL * Le);
                 else charge(acc, A, n_rgb, dL * Le);
                 if (Bm) Le_b = Le;
+                if constexpr (Em) {
+                    if (active_next) {
+                        const V3 dE = (dL * (beta * mis)) * emitter_eval_mask(S, em, si);
+                        if (Det) add_slot(Pp, q.emitter_slot()[em], dE);
+                        else add_slot(acc, q.emitter_slot()[em], dE);
+                    }
+                }
             }
             active_next = active_next && (depth + 1 < in.max_depth) && si.valid;
             const bool active_em0 = active_next && smooth;
@@ -1410,9 +1438,15 @@ k_wf_bounce_prb(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value,
             ds.d = v3(0, 0, 0);
             ds.delta = false;
             V3 em_weight = v3(0, 0, 0);
+            int32_t em_slot = -1;    // Em: the sampled emitter's slot and d em_weight / d radiance
+            float em_inv_pdf = 0.f;
             if (active_em0) {
                 em_weight = scene_sample_emitter_direction(S, si.p, e0, e1, ds);
-                if (ds.pdf != 0.f && nonzero(em_weight)) {
+                if constexpr (Em) {  // a zero-weight sample of a differentiated emitter still needs its visibility
+                    em_slot = S.n_emitters ? q.emitter_slot()[sampled_emitter(S, e0)] : -1;
+                    if (em_slot >= 0) em_inv_pdf = emitter_sample_inv_pdf(S, sampled_emitter(S, e0), ds);
+                }
+                if (ds.pdf != 0.f && (nonzero(em_weight) || (Em && em_inv_pdf != 0.f))) {
                     shadow = true;
                     sray = spawn_ray_to(si.p, si.n, ds.p);
                 }
@@ -1444,6 +1478,7 @@ k_wf_bounce_prb(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value,
                 }
                 if (slot >= 0 && si.wi.z > 0.f && wo_em.z > 0.f)
                     add_slot(G, slot, (((dL * em_weight) * beta_mis_em) * wo_em.z) * kInvPi);
+                if constexpr (Em) add_slot(G, em_slot, (dL * (beta_mis_em * bsdf_value_em)) * em_inv_pdf);
                 if (Bm) {
                     Lr_pot = Lr;
                     if (bvtx && si.wi.z > 0.f && wo_em.z > 0.f)
@@ -1606,12 +1641,19 @@ struct WfFwdOut {
     float *out;          // sample planes: L.r L.g L.b pos.x pos.y [alpha]
     uint64_t plane;      // floats between planes
     int alpha;
+    uint32_t emitter_off;  // GradArgs::emitter_off (read by the Em instances only)
     const int32_t *slot_of_tex;
     float *const *tan;   // per slot: tangent values (rgb: 3, bitmap: the texels)
     const uint32_t *is_rgb;
+    MH_DEV const int32_t *emitter_slot() const {  // emitter -> slot of its radiance tangent or -1
+        return reinterpret_cast<const int32_t *>(reinterpret_cast<const uint8_t *>(slot_of_tex) + emitter_off);
+    }
 };
 
-template <bool Gen>
+// Em: an emitter's radiance carries a tangent t_e (WfFwdOut::emitter_slot()):
+// a direct hit adds beta mis mask t_e, an unoccluded emitter sample
+// beta mis_em bsdf / pdf t_e
+template <bool Gen, bool Em = false>
 __global__ void __launch_bounds__(256, MH_BOUNCE_PRB_WAVES)
 k_wf_bounce_fwd(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value, WfState w, WfPrb q, int cur,
                 uint32_t seg_cap, uint32_t *ctr, uint32_t *ctr_next, uint64_t n_total, WfFwdOut fo) {
@@ -1704,6 +1746,9 @@ k_wf_bounce_fwd(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value,
                 if (active_next)
                     le = emitter_eval(S, em, si);
                 dL = dL + ((beta * mis) * le) * (T * kInvPi);
+                if constexpr (Em) {
+                    if (active_next) dL = dL + ((beta * mis) * emitter_eval_mask(S, em, si)) * emitter_tangent(tg, fo.emitter_slot()[em]);
+                }
             }
             active_next = active_next && (depth + 1 < in.max_depth) && si.valid;
             const bool active_em0 = active_next && smooth;
@@ -1713,9 +1758,15 @@ k_wf_bounce_fwd(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value,
             ds.d = v3(0, 0, 0);
             ds.delta = false;
             V3 em_weight = v3(0, 0, 0);
+            int32_t em_slot = -1;    // Em: the sampled emitter's slot and d em_weight / d radiance
+            float em_inv_pdf = 0.f;
             if (active_em0) {
                 em_weight = scene_sample_emitter_direction(S, si.p, e0, e1, ds);
-                if (ds.pdf != 0.f && nonzero(em_weight)) {
+                if constexpr (Em) {  // a zero-weight sample of a differentiated emitter still needs its visibility
+                    em_slot = S.n_emitters ? fo.emitter_slot()[sampled_emitter(S, e0)] : -1;
+                    if (em_slot >= 0) em_inv_pdf = emitter_sample_inv_pdf(S, sampled_emitter(S, e0), ds);
+                }
+                if (ds.pdf != 0.f && (nonzero(em_weight) || (Em && em_inv_pdf != 0.f))) {
                     shadow = true;
                     sray = spawn_ray_to(si.p, si.n, ds.p);
                 }
@@ -1734,6 +1785,7 @@ k_wf_bounce_fwd(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value,
                 G = ((beta_mis_em * bsdf_value_em) * em_weight) * (T * kInvPi);
                 if (tvtx && si.wi.z > 0.f && wo_em.z > 0.f)
                     G = G + (((em_weight * beta_mis_em) * wo_em.z) * kInvPi) * t;
+                if constexpr (Em) G = G + ((beta_mis_em * bsdf_value_em) * em_inv_pdf) * emitter_tangent(tg, em_slot);
             }
             (void)rng.next_float();
             float s2x = rng.next_float(), s2y = rng.next_float();
@@ -1792,7 +1844,7 @@ hipError_t launch_wavefront_fwd(const DScene &S, const IntegratorParams &in, con
                                 uint64_t n, const int32_t *slot_of_tex, float *const *tangents,
                                 const uint32_t *is_rgb, float *out, uint64_t plane, int alpha, void *ws,
                                 void *ws_prb, uint64_t cap, uint32_t *ctr, uint32_t n_bounces, uint32_t grid,
-                                hipStream_t st) {
+                                hipStream_t st, uint32_t emitter_off) {
     if (n == 0) return hipSuccess;
     if (n > (1ull << kPidBits) || n_bounces > kMaxWfBounces || !wf_fused(S)) return hipErrorInvalidValue;
     WfState w = carve(ws, cap);
@@ -1801,16 +1853,21 @@ hipError_t launch_wavefront_fwd(const DScene &S, const IntegratorParams &in, con
     if (e != hipSuccess) return e;
     const uint32_t seg_cap = seg_len(n);
     const size_t sh_fused = fused_lds_bytes(S);
-    const WfFwdOut fo{out, plane, alpha, slot_of_tex, tangents, is_rgb};
+    const WfFwdOut fo{out, plane, alpha, emitter_off, slot_of_tex, tangents, is_rgb};
     for (uint32_t b = 0; b < n_bounces; ++b) {
         uint32_t *c = ctr + kCtrStride * b, *cn = ctr + kCtrStride * (b + 1);
         const int cur = (int)(b & 1);
-        if (b == 0)
-            hipLaunchKernelGGL(k_wf_bounce_fwd<true>, dim3(grid), dim3(256), sh_fused, st, S, in, lm, seed_value, w, q,
-                               cur, seg_cap, c, cn, n, fo);
-        else
-            hipLaunchKernelGGL(k_wf_bounce_fwd<false>, dim3(grid), dim3(256), sh_fused, st, S, in, lm, seed_value, w,
-                               q, cur, seg_cap, c, cn, n, fo);
+#define MH_BOUNCE_FWD(GEN, EM)                                                                                  \
+    hipLaunchKernelGGL((k_wf_bounce_fwd<GEN, EM>), dim3(grid), dim3(256), sh_fused, st, S, in, lm, seed_value, w, q, \
+                       cur, seg_cap, c, cn, n, fo)
+        if (emitter_off) {
+            if (b == 0) MH_BOUNCE_FWD(true, true);
+            else MH_BOUNCE_FWD(false, true);
+        } else {
+            if (b == 0) MH_BOUNCE_FWD(true, false);
+            else MH_BOUNCE_FWD(false, false);
+        }
+#undef MH_BOUNCE_FWD
     }
     return hipGetLastError();
 }
@@ -2077,11 +2134,12 @@ hipError_t launch_wavefront_prb(const DScene &S, const IntegratorParams &in, con
                                 const float *weights, const int32_t *slot_of_tex, uint32_t n_rgb,
                                 void *ws, void *ws_prb, uint64_t cap, uint32_t *ctr, uint32_t n_bounces,
                                 uint32_t grid, float *partial, hipStream_t st, hipEvent_t *span,
-                                const WfBitmapArgs *bmp, void *ws_det) {
+                                const WfBitmapArgs *bmp, void *ws_det, uint32_t emitter_off) {
     if (n == 0) return hipSuccess;
     if (n > (1ull << kPidBits) || n_bounces > kMaxWfBounces || n_rgb > (uint32_t)kMaxRgbParams) return hipErrorInvalidValue;
     WfState w = carve(ws, cap);
-    WfPrb q = carve_prb(ws_prb, cap, partial, slot_of_tex, n_rgb);
+    WfPrb q = carve_prb(ws_prb, cap, partial, slot_of_tex, n_rgb, emitter_off);
+    const bool em = emitter_off != 0;  // selects the Em instances; a call without an emitter parameter launches the others
     hipError_t e = hipMemsetAsync(ctr, 0, sizeof(uint32_t) * kCtrStride * (n_bounces + 1), st);
     if (e != hipSuccess) return e;
     const bool lds = S.lds_bytes_bvh != 0, packet = use_packet(S);
@@ -2108,14 +2166,19 @@ hipError_t launch_wavefront_prb(const DScene &S, const IntegratorParams &in, con
 #ifdef MH_EXP_BPHASE
     g_prb_ring_lds = sh_fused + (prb_nee_ring<1, false, false, false>() ? 4u * kNeeRingFloats * 4u : 0u);
 #endif
-#define MH_BOUNCE_PRB(NR, GEN, BM, DET)                                                                        \
-    hipLaunchKernelGGL((k_wf_bounce_prb<NR, GEN, BM, DET>),                                                    \
+#define MH_BOUNCE_PRB(NR, GEN, BM, DET, EM)                                                                    \
+    hipLaunchKernelGGL((k_wf_bounce_prb<NR, GEN, BM, DET, EM>),                                                \
                        dim3(grid), dim3(256),      \
                        sh_fused + (prb_nee_ring<NR, GEN, BM, DET>() ? 4u * kNeeRingFloats * 4u : 0u), st, S, in, lm, seed_value, w, q, cur, seg_cap, c, cn, gen, bm, det)
 #define MH_BOUNCE_PRB_NR(GEN, BM, DET)                                                                         \
     do {                                                                                                       \
-        if (n_rgb <= 1) MH_BOUNCE_PRB(1, GEN, BM, DET);                                                        \
-        else MH_BOUNCE_PRB(kMaxRgbParams, GEN, BM, DET);                                                       \
+        if (em) {                                                                                              \
+            if (n_rgb <= 1) MH_BOUNCE_PRB(1, GEN, BM, DET, true);                                              \
+            else MH_BOUNCE_PRB(kMaxRgbParams, GEN, BM, DET, true);                                             \
+        } else {                                                                                               \
+            if (n_rgb <= 1) MH_BOUNCE_PRB(1, GEN, BM, DET, false);                                             \
+            else MH_BOUNCE_PRB(kMaxRgbParams, GEN, BM, DET, false);                                            \
+        }                                                                                                      \
     } while (0)
     for (uint32_t b = 0; b < n_bounces; ++b) {
         uint32_t *c = ctr + kCtrStride * b, *cn = ctr + kCtrStride * (b + 1);
@@ -2137,21 +2200,23 @@ hipError_t launch_wavefront_prb(const DScene &S, const IntegratorParams &in, con
             continue;
         }
         MH_WF_DISPATCH(k_wf_trace, S, w, cur, seg_cap, c);
+#define MH_SHADE_PRB(STAGED, NR, EM)                                                                           \
+    hipLaunchKernelGGL((k_wf_shade_prb<STAGED, NR, EM>), dim3(grid), dim3(256), STAGED ? S.tab_bytes : 0, st, S, in, \
+                       lm, seed_value, w, q, cur, seg_cap, c, cn)
+#define MH_SHADE_PRB_EM(STAGED, NR)                                                                            \
+    do {                                                                                                       \
+        if (em) MH_SHADE_PRB(STAGED, NR, true);                                                                \
+        else MH_SHADE_PRB(STAGED, NR, false);                                                                  \
+    } while (0)
         if (n_rgb == 1) {
-            if (S.tab_bytes)
-                hipLaunchKernelGGL((k_wf_shade_prb<true, 1>), dim3(grid), dim3(256), S.tab_bytes, st, S, in, lm,
-                                   seed_value, w, q, cur, seg_cap, c, cn);
-            else
-                hipLaunchKernelGGL((k_wf_shade_prb<false, 1>), dim3(grid), dim3(256), 0, st, S, in, lm, seed_value,
-                                   w, q, cur, seg_cap, c, cn);
+            if (S.tab_bytes) MH_SHADE_PRB_EM(true, 1);
+            else MH_SHADE_PRB_EM(false, 1);
         } else {
-            if (S.tab_bytes)
-                hipLaunchKernelGGL((k_wf_shade_prb<true, kMaxRgbParams>), dim3(grid), dim3(256), S.tab_bytes, st, S,
-                                   in, lm, seed_value, w, q, cur, seg_cap, c, cn);
-            else
-                hipLaunchKernelGGL((k_wf_shade_prb<false, kMaxRgbParams>), dim3(grid), dim3(256), 0, st, S, in, lm,
-                                   seed_value, w, q, cur, seg_cap, c, cn);
+            if (S.tab_bytes) MH_SHADE_PRB_EM(true, kMaxRgbParams);
+            else MH_SHADE_PRB_EM(false, kMaxRgbParams);
         }
+#undef MH_SHADE_PRB_EM
+#undef MH_SHADE_PRB
         if (n_rgb == 1) MH_WF_DISPATCH_NR(k_wf_shadow_prb, 1, S, w, q, seg_cap, c);
         else MH_WF_DISPATCH_NR(k_wf_shadow_prb, kMaxRgbParams, S, w, q, seg_cap, c);
     }

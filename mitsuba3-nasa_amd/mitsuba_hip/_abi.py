@@ -47,10 +47,11 @@ MEDIUM_HETEROGENEOUS, MEDIUM_HOMOGENEOUS = 0, 1
 PHASE_ISOTROPIC, PHASE_HG = 0, 1
 MEDIUM_NO_EMITTER_SAMPLING, MEDIUM_NO_SPECTRAL_EXTINCTION = 1, 2
 INTEGRATOR_PATH, INTEGRATOR_VOLPATH, INTEGRATOR_PRB, INTEGRATOR_PRBVOLPATH = 0, 1, 2, 3
-# differentiable parameter ids of mh_render_backward (texture index, or kind | medium)
+# differentiable parameter ids of mh_render_backward (texture index, or kind | medium / emitter)
 PARAM_KIND_MASK = 0xF0000000
 PARAM_MEDIUM_SIGMA_T = 0x10000000
 PARAM_MEDIUM_ALBEDO = 0x20000000
+PARAM_EMITTER_RADIANCE = 0x30000000
 
 FLAG_DEVICE_POINTERS = 1 << 0
 FLAG_ACCUMULATE = 1 << 1
@@ -142,7 +143,7 @@ EXPORTS = [
     "mh_scene_bvh_info", "mh_render_samples", "mh_scene_update_medium", "mh_trace_preliminary",
     "mh_render_forward", "mh_comm_unique_id", "mh_comm_create", "mh_comm_create_all", "mh_comm_destroy",
     "mh_comm_info", "mh_comm_reduce", "mh_scene_set_comm", "mh_scene_synchronize", "mh_render_sharded",
-    "mh_render_backward_sharded",
+    "mh_render_backward_sharded", "mh_scene_update_emitter",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -182,6 +183,7 @@ def lib():
     L.mh_scene_update_rgb.argtypes = [vp, u32, PF]
     L.mh_scene_update_texture.argtypes = [vp, u32, PF, u64]
     L.mh_scene_update_medium.argtypes = [vp, u32, vp, vp, vp, u64, u32]
+    L.mh_scene_update_emitter.argtypes = [vp, u32, PF]
     L.mh_render.argtypes = [vp, C.POINTER(Integrator), u32, u32, u32, u32, vp, u32, C.POINTER(Stats)]
     L.mh_develop.argtypes = [vp, vp, vp, u32]
     L.mh_render_samples.argtypes = [vp, C.POINTER(Integrator), u32, u32, u32, u32, vp, u32]

@@ -63,7 +63,9 @@ class SceneParameters:
     parameters on the hot path: '<bsdf>.reflectance.value' / '.data' and the
     medium parameters '<medium>.sigma_t.data' (grid, shape (z, y, x, 1) as the
     reference's TensorXf), '<medium>.sigma_t.value' (homogeneous) and
-    '<medium>.albedo.value'."""
+    '<medium>.albedo.value', and the emitters' radiance:
+    '<shape>.emitter.radiance.value' (area), '<name>.radiance.value'
+    (constant) and '<name>.irradiance.value' (directional)."""
 
     def __init__(self, scene: Scene, device=None):
         torch = _torch()
@@ -84,6 +86,8 @@ class SceneParameters:
                 v = torch.tensor([scene.medium(idx).sigma_t_const], dtype=torch.float32)
             elif kind == "medium_albedo":
                 v = torch.tensor(list(scene.medium(idx).albedo), dtype=torch.float32)
+            elif kind == "emitter_radiance":
+                v = torch.tensor(list(scene.emitter(idx).radiance), dtype=torch.float32)
             else:
                 continue
             if device is not None:
@@ -128,6 +132,8 @@ class SceneParameters:
             return A.PARAM_MEDIUM_SIGMA_T | idx
         if kind == "medium_albedo":
             return A.PARAM_MEDIUM_ALBEDO | idx
+        if kind == "emitter_radiance":
+            return A.PARAM_EMITTER_RADIANCE | idx
         return idx
 
     def update(self, values: Optional[Dict] = None):
@@ -144,6 +150,10 @@ class SceneParameters:
                 self.scene.texture(idx).value[:] = [float(x) for x in arr]
                 for h in self.scene._handles.values():
                     A.check(L.mh_scene_update_rgb(h, idx, arr.ctypes.data_as(A.PF)))
+            elif kind == "emitter_radiance":
+                self.scene.emitter(idx).radiance[:] = [float(x) for x in arr]
+                for h in self.scene._handles.values():
+                    A.check(L.mh_scene_update_emitter(h, idx, arr.ctypes.data_as(A.PF)))
             elif kind in ("grid", "medium_sigma_t", "medium_albedo"):
                 m = self.scene.medium(idx)
                 if kind == "grid":

@@ -601,6 +601,9 @@ class Scene:
     def medium(self, idx: int) -> A.Medium:
         return self._media[idx]
 
+    def emitter(self, idx: int) -> A.Emitter:
+        return self._emitters[idx]
+
     def grid_data(self, idx: int) -> np.ndarray:
         m = self._media[idx]
         n = m.grid_res[0] * m.grid_res[1] * m.grid_res[2]
