@@ -20,7 +20,9 @@
 #include <rocprofiler-sdk-roctx/roctx.h>
 
 #include "mh_device.hpp"
+#include "mh_env.hpp"
 #include "mh_internal.hpp"
+#include "mh_plan.hpp"
 #include "mh_shading.hpp"
 
 // The reference's ProfilerPhase scopes (include/mitsuba/core/profiler.h:20-47,
@@ -97,6 +99,13 @@ hipError_t upload(DevBuf &b, const T *src, size_t count, hipStream_t st) {
     if (e != hipSuccess) return e;
     if (src && count) return hipMemcpyAsync(b.ptr, src, sizeof(T) * count, hipMemcpyHostToDevice, st);
     return hipMemsetAsync(b.ptr, 0, bytes, st);
+}
+
+// compute units of a device (256, an MI355X's, if the query fails)
+int device_cus(int device) {
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+    return cus;
 }
 
 }  // namespace
@@ -267,9 +276,8 @@ int mh_scene_create(const mh_scene_desc *desc, int device, void *stream, mh_scen
         // (12, C_t = 4); otherwise the per-lane engine (8, C_t = 2).  Leaf counts
         // <= 31 (5-bit field of the stream engine's stack entries); env overrides.
         const bool small = bp.size() <= 64;
-        const char *el = getenv("MH_BVH_LEAF"), *ec = getenv("MH_BVH_CT");
-        uint32_t max_leaf = el ? (uint32_t)std::max(2, std::min(31, atoi(el))) : (small ? 12u : 8u);
-        float ct = ec ? (float)atof(ec) : (small ? 4.0f : 2.0f);
+        uint32_t max_leaf = (uint32_t)env::bvh_leaf(small ? 12 : 8);
+        float ct = (float)env::bvh_ct(small ? 4.0 : 2.0);
         ScopedPhase accel_("InitAccel");
         build_bvh(bp, bvh, max_leaf, ct);
     }
@@ -469,11 +477,10 @@ int mh_scene_create(const mh_scene_desc *desc, int device, void *stream, mh_scen
         // the float BVH4 (round 1); MH_BVH4Q=1: the quantised BVH4 + compact
         // primitives (round 4, measured slower so far: DESIGN.md §3);
         // MH_BVH4=0: BVH2
-        const char *e4 = getenv("MH_BVH4"), *eq = getenv("MH_BVH4Q");
-        if (S.lds_bytes_bvh == 0 && bvh.n_prims > 64 && !(e4 && !strcmp(e4, "0"))) {
+        if (S.lds_bytes_bvh == 0 && bvh.n_prims > 64 && !env::bvh4_off()) {
             std::vector<uint8_t> n4, pc;
             uint32_t cnt4 = 0, depth4 = 0;
-            const bool quant = (eq && !strcmp(eq, "1")) && build_qbvh4(bvh, n4, pc, cnt4, depth4);
+            const bool quant = env::bvh4q() && build_qbvh4(bvh, n4, pc, cnt4, depth4);
             if (!quant) collapse_bvh4(bvh, n4, cnt4, depth4);
             const uint32_t stack4 = 3u * depth4 + 2u;
             if ((size_t)std::max(S.stack_size, stack4) * 256 * 4 <= 65536 &&
@@ -485,8 +492,7 @@ int mh_scene_create(const mh_scene_desc *desc, int device, void *stream, mh_scen
                 } else {
                     S.nodes4 = reinterpret_cast<const Node4 *>(s->nodes4.ptr);
                     // MH_PRIMC=1: the compact 48-B triangle records with the float BVH4
-                    const char *epc = getenv("MH_PRIMC");
-                    if (epc && !strcmp(epc, "1")) {
+                    if (env::primc()) {
                         std::vector<uint8_t> qn, pc2;
                         uint32_t c2 = 0, d2 = 0;
                         if (build_qbvh4(bvh, qn, pc2, c2, d2) && upload(s->primsc, pc2.data(), pc2.size(), st) == hipSuccess)
@@ -512,12 +518,9 @@ int mh_scene_create(const mh_scene_desc *desc, int device, void *stream, mh_scen
     S.stack_ovf = nullptr;
     S.ovf_threads = 0;
     if (S.lds_bytes_bvh == 0 && (S.nodes4 || S.qnodes)) {
-        const char *es = getenv("MH_STREAM_STACK");
-        const uint32_t cap = es ? (uint32_t)std::max(4, atoi(es)) : 20u;
+        const uint32_t cap = (uint32_t)env::stream_stack(20);
         if (cap < S.stack_size) {
-            int cus = 256;
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-            const uint32_t threads = wf_blocks(cus) * 256u;
+            const uint32_t threads = wf_blocks(device_cus(device)) * 256u;
             if (upload(s->stack_ovf, (const uint32_t *)nullptr, (size_t)(S.stack_size - cap) * threads, st) == hipSuccess) {
                 S.stream_stack = cap;
                 S.stack_ovf = s->stack_ovf.as<uint32_t>();
@@ -763,17 +766,8 @@ constexpr int kCtrAuxItems = 26;
 // the device half of the contract: a non-zero bounds counter fails the call
 static int check_bounds_counter(mh_scene *s, const char *api);
 // prbvolpath backward grid (MH_VOL_WAVES = 4 waves / SIMD: 4 workgroups per CU)
-// and NEE-log entries per thread (16 B each; longer walks replay)
-constexpr uint32_t kPvpBlocksPerCu = 4, kPvpNeeCap = 256;
-// MainLog entries per thread (64 B each: 4 GiB over the 262,144 threads of a
-// 256-CU grid, less when the render has fewer samples than threads); a path
-// with more logged vertices replays its adjoint
-constexpr uint32_t kPvpMainCap = 256;
-// MH_FLAG_DETERMINISTIC or MH_DETERMINISTIC=1: fixed-order splat (k_splat_gather)
-static bool deterministic(uint32_t flags) {
-    const char *e = getenv("MH_DETERMINISTIC");
-    return (flags & MH_FLAG_DETERMINISTIC) || (e && !strcmp(e, "1"));
-}
+// (the log entries per thread: kPvpNeeCap, kPvpMainCap of mh_plan.hpp)
+constexpr uint32_t kPvpBlocksPerCu = 4;
 
 static double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch())
@@ -865,11 +859,7 @@ static bool async_call(uint32_t flags, const mh_stats *stats) {
 // (the caller already runs another call beside this one).  A single-chunk
 // call of at least kTwoStreamMinSamples samples is split into two chunks.
 // MH_WF_STREAMS=1 keeps one stream (measurements, the bench's roofline pass).
-constexpr uint64_t kTwoStreamMinSamples = 1ull << 19;
-static bool chunk_streams_enabled() {
-    const char *e = getenv("MH_WF_STREAMS");
-    return !(e && !strcmp(e, "1"));
-}
+// Whether a call uses it is the planner's decision (mh_plan.hpp split_chunks).
 
 // stream2 (created on first use, on the scene's device) waits for the work
 // enqueued on st so far
@@ -887,6 +877,53 @@ static hipError_t join_stream(mh_scene *s, hipStream_t st) {
     hipError_t e = hipEventRecord(s->ev_join, s->stream2);
     if (e == hipSuccess) e = hipStreamWaitEvent(st, s->ev_join, 0);
     return e;
+}
+
+// the splat's fast path: >= 4 spp and the default-sized Gaussian filter
+static bool fast_splat(const Layout &L, const DScene &S) {
+    return L.spp_pp >= 4 && S.rfilter == MH_RFILTER_GAUSSIAN && S.rfilter_radius > 1.5f && S.rfilter_radius <= 2.5f;
+}
+
+// Film storage of mh_render / mh_render_forward: RGBW, or R G B A W for alpha
+// films; the kernels splat into an RGBW film (film4, + an alpha plane film_a)
+// that an alpha film receives at the end (launch_film_rgbaw).  Zeroed, or
+// holding the caller's film with MH_FLAG_ACCUMULATE.
+struct FilmStage {
+    bool alpha = false;
+    size_t bytes = 0;
+    float *film = nullptr, *film4 = nullptr, *film_a = nullptr;
+};
+static int stage_film(mh_scene *s, uint64_t n_px, float *film_rgbw, uint32_t flags, hipStream_t st, FilmStage &F) {
+    F.alpha = has_alpha(s->pixel_format);
+    F.bytes = n_px * (F.alpha ? 20 : 16);
+    F.film = film_rgbw;
+    if (!(flags & MH_FLAG_DEVICE_POINTERS)) {
+        MH_HIP(s->film_tmp.alloc(F.bytes));
+        F.film = s->film_tmp.as<float>();
+    }
+    if (!(flags & MH_FLAG_ACCUMULATE)) MH_HIP(hipMemsetAsync(F.film, 0, F.bytes, st));
+    else if (!(flags & MH_FLAG_DEVICE_POINTERS))
+        MH_HIP(hipMemcpyAsync(F.film, film_rgbw, F.bytes, hipMemcpyHostToDevice, st));
+    F.film4 = F.film;
+    if (F.alpha) {
+        MH_HIP(s->film4.alloc(n_px * 16));
+        MH_HIP(s->alpha_px.alloc(n_px * 4));
+        F.film4 = s->film4.as<float>();
+        F.film_a = s->alpha_px.as<float>();
+        MH_HIP(hipMemsetAsync(F.film4, 0, n_px * 16, st));
+        MH_HIP(hipMemsetAsync(F.film_a, 0, n_px * 4, st));
+    }
+    return MH_OK;
+}
+
+// what the planners (mh_plan.hpp) need to know of a call and its scene
+static plan::Facts call_facts(const mh_scene *s, const mh_integrator &in, uint32_t flags, uint64_t n_px, uint32_t spp) {
+    plan::Facts f;
+    f.type = in.type; f.max_depth = in.max_depth; f.flags = flags;
+    f.n_px = n_px; f.spp = spp;
+    f.wf_fused = wf_fused(s->S); f.vs_ok = vs_supported(s->S, in); f.vw_ok = vw_supported(s->S, in);
+    f.wf_max = wf_max_chunk(); f.vw_max = vw_max_chunk();
+    return f;
 }
 
 static int render_impl(mh_scene *s, const mh_integrator *in, uint32_t seed, uint32_t spp, uint32_t spp_begin,
@@ -910,73 +947,43 @@ static int render_impl(mh_scene *s, const mh_integrator *in, uint32_t seed, uint
     // test hook of the communicator's failure semantics (tests/test_gpu_comm.py,
     // documented in INTEGRATION.md): a reducing call (MH_FLAG_REDUCE) fails
     // after it was issued.  Calls without a collective never read it.
-    if ((flags & MH_FLAG_REDUCE) && getenv("MH_TEST_FAIL_AFTER_ISSUE"))
+    if ((flags & MH_FLAG_REDUCE) && env::test_fail_after_issue())
         return set_error(MH_ERR_HIP, "MH_TEST_FAIL_AFTER_ISSUE: injected failure");
     hipStream_t st = s->stream;
     const uint64_t n_px = (uint64_t)L.W * L.H;
-    // film storage: RGBW, or R G B A W for alpha films; the kernels splat into
-    // an RGBW film (+ an alpha plane) that an alpha film receives at the end
-    const bool alpha = has_alpha(s->pixel_format);
-    const size_t film_bytes = n_px * (alpha ? 20 : 16);
-    float *film = film_rgbw;
-    if (!(flags & MH_FLAG_DEVICE_POINTERS)) {
-        MH_HIP(s->film_tmp.alloc(film_bytes));
-        film = s->film_tmp.as<float>();
-    }
-    if (!(flags & MH_FLAG_ACCUMULATE) || !(flags & MH_FLAG_DEVICE_POINTERS)) {
-        if (!(flags & MH_FLAG_ACCUMULATE)) MH_HIP(hipMemsetAsync(film, 0, film_bytes, st));
-        else MH_HIP(hipMemcpyAsync(film, film_rgbw, film_bytes, hipMemcpyHostToDevice, st));
-    }
-    float *film4 = film, *film_a = nullptr;
-    if (alpha) {
-        MH_HIP(s->film4.alloc(n_px * 16));
-        MH_HIP(s->alpha_px.alloc(n_px * 4));
-        film4 = s->film4.as<float>();
-        film_a = s->alpha_px.as<float>();
-        MH_HIP(hipMemsetAsync(film4, 0, n_px * 16, st));
-        MH_HIP(hipMemsetAsync(film_a, 0, n_px * 4, st));
-    }
+    FilmStage F;
+    if (int rc = stage_film(s, n_px, film_rgbw, flags, st, F)) return rc;
+    const bool alpha = F.alpha;
+    const size_t film_bytes = F.bytes;
+    float *const film = F.film, *const film4 = F.film4, *const film_a = F.film_a;
     MH_HIP(hipMemsetAsync(s->counters.ptr, 0, 256, st));
     const uint32_t S_ = L.s_end - L.s_begin;
     const uint64_t per_pixel = (uint64_t)S_ * L.n_passes;
-    // execution mode: wavefront for `path` (bounded depth; several passes only
-    // on the fused bounce kernel, which carries each lane's PCG32 state from
-    // one pass to the next) unless forced
-    bool wavefront = in->type == MH_INTEGRATOR_PATH && in->max_depth <= 64 && (L.n_passes == 1 || wf_fused(s->S));
-    // volpath: main / walk rounds (mh_volwave.hip), single pass
-    bool volwave = (vol_sched_mode() ? vs_supported(s->S, *in) : vw_supported(s->S, *in)) && L.n_passes == 1;
-    const char *env_mode = getenv("MH_MODE");
-    if (env_mode && !strcmp(env_mode, "mega")) wavefront = volwave = false;
-    if (flags & MH_FLAG_MEGAKERNEL) wavefront = volwave = false;
-    if ((flags & MH_FLAG_WAVEFRONT) && !wavefront && !volwave)
-        return set_error(MH_ERR_UNSUPPORTED, "mh_render: the wavefront mode supports the 'path' integrator "
-                                             "with max_depth <= 64 (several passes: packet-engine scenes) and "
-                                             "'volpath' with max_depth <= 1024 (one pass)");
-    uint64_t max_samples = volwave ? vw_max_chunk() : 1ull << 25;
-    if (wavefront) {
-        const char *ec = getenv("MH_WF_CHUNK");
-        max_samples = std::min<uint64_t>(wf_max_chunk(), ec ? std::max<uint64_t>(1024, strtoull(ec, nullptr, 10)) : wf_max_chunk());
-    }
-    uint32_t chunk_px = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_px, max_samples / per_pixel));
-    // (the unfused stream-engine kernels of large meshes too: stream2's launches
-    // get their own stack overflow columns, S2 below)
-    const bool two_ok = wavefront && !deterministic(flags) && !(flags & MH_FLAG_SHARED_DEVICE) &&
-                        chunk_streams_enabled();
-    if (two_ok && chunk_px >= n_px && n_px >= 2 && n_px * per_pixel >= kTwoStreamMinSamples)
-        chunk_px = (uint32_t)((n_px + 1) / 2);
-    const bool two = two_ok && chunk_px < n_px;
+    // execution mode, chunks and streams (mh_plan.hpp)
+    plan::Facts facts = call_facts(s, *in, flags, n_px, S_);
+    facts.n_passes = L.n_passes;
+    facts.vol_sched = vol_sched_mode();
+    const plan::RenderPlan plan = plan::plan_render(facts, env::plan_env(env::Call::Render));
+    if (plan.err)
+        return set_error(plan.err, "mh_render: the wavefront mode supports the 'path' integrator "
+                                   "with max_depth <= 64 (several passes: packet-engine scenes) and "
+                                   "'volpath' with max_depth <= 1024 (one pass)");
+    const bool wavefront = plan.wavefront, volwave = plan.volwave, sched = plan.sched;
+    const bool vw_debug = env::vw_debug();
+    // (two streams: stream2's launches get their own stack overflow columns, S2 below)
+    const uint32_t chunk_px = plan.chunks.chunk_px;
+    const bool two = plan.chunks.two;
     const uint64_t plane = (uint64_t)chunk_px * per_pixel;
     MH_HIP(s->work.alloc(plane * (alpha ? 6 : 5) * sizeof(float)));
     if (two) MH_HIP(s->work2.alloc(plane * (alpha ? 6 : 5) * sizeof(float)));
-    const bool fast_splat = L.spp_pp >= 4 && s->S.rfilter == MH_RFILTER_GAUSSIAN &&
-                            s->S.rfilter_radius > 1.5f && s->S.rfilter_radius <= 2.5f;
+    const bool fast = fast_splat(L, s->S);
     const int coalesce = L.spp_pp >= 4;
     const uint32_t seed_value = s->S.sampler_seed + seed;
-    const bool determ = deterministic(flags);
+    const bool determ = plan.determ;
     unsigned long long *invalid = s->counters.as<unsigned long long>() + kCtrInvalid;
     unsigned long long *bounds = s->counters.as<unsigned long long>() + kCtrBounds;
     float kernel_ms = 0.f, trace_ms = 0.f;
-    const size_t n_chunks = (size_t)((n_px + chunk_px - 1) / chunk_px);
+    const size_t n_chunks = (size_t)plan.chunks.n_chunks;
     const uint32_t n_bounces = wavefront ? in->max_depth : 0;
     const size_t ev_per_chunk = 3 + 2 * n_bounces;  // integrator span, bounce spans, splat end
     while (s->evpool.size() < ev_per_chunk * n_chunks) {
@@ -986,8 +993,7 @@ static int render_impl(mh_scene *s, const mh_integrator *in, uint32_t seed, uint
     }
     const size_t ctr_words = wavefront ? wf_counter_words(n_bounces) : 0;  // per pass
     const size_t ctr_per_chunk = ctr_words * L.n_passes;
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device);
+    const int cus = device_cus(s->device);
     if (wavefront) {
         MH_HIP(s->wf_ws.alloc(wf_workspace_bytes(plane)));
         MH_HIP(s->wf_ctr.alloc(std::max<size_t>(16, ctr_per_chunk * n_chunks * 4)));
@@ -1003,7 +1009,7 @@ static int render_impl(mh_scene *s, const mh_integrator *in, uint32_t seed, uint
         S2.stack_ovf = s->stack_ovf2.as<uint32_t>();
     }
     if (two) MH_HIP(fork_stream(s, st));
-    if (volwave && !vol_sched_mode()) {
+    if (volwave && !sched) {
         MH_HIP(s->wf_ws.alloc(vw_workspace_bytes(plane)));
         MH_HIP(s->wf_ctr.alloc((size_t)vw_counter_words(vw_rounds(*in)) * 4));
     }
@@ -1027,7 +1033,7 @@ static int render_impl(mh_scene *s, const mh_integrator *in, uint32_t seed, uint
                                     L.n_passes,
                                     L.n_passes > 1 ? (odd ? s->wf_carry2 : s->wf_carry).as<uint64_t>() : nullptr,
                                     alpha));
-        } else if (volwave && vol_sched_mode()) {
+        } else if (sched) {
             MH_HIP(launch_vol_sched(s->S, *in, lm, seed_value, n, plane, s->work.as<float>(), vs_blocks(cus),
                                     s->counters.as<unsigned long long>(), st, alpha));
         } else if (volwave) {
@@ -1041,10 +1047,10 @@ static int render_impl(mh_scene *s, const mh_integrator *in, uint32_t seed, uint
         }
         MH_HIP(hipEventRecord(ev[1], cs));
         ScopedPhase put_("ImageBlockPut");
-        MH_SPLAT(s->S, lm, kSplatFilm, fast_splat, npx, L.n_passes, n, plane, work.as<float>(), film4,
+        MH_SPLAT(s->S, lm, kSplatFilm, fast, npx, L.n_passes, n, plane, work.as<float>(), film4,
                  seed_value, coalesce, cs, invalid, determ, work.bytes / 4, n_px * 4, bounds);
         if (alpha)
-            MH_SPLAT(s->S, lm, kSplatAlpha, fast_splat, npx, L.n_passes, n, plane, work.as<float>(), film_a,
+            MH_SPLAT(s->S, lm, kSplatAlpha, fast, npx, L.n_passes, n, plane, work.as<float>(), film_a,
                      seed_value, coalesce, cs, nullptr, determ, work.bytes / 4, n_px, bounds);
         MH_HIP(hipEventRecord(ev[ev_per_chunk - 1], cs));
     }
@@ -1056,7 +1062,7 @@ static int render_impl(mh_scene *s, const mh_integrator *in, uint32_t seed, uint
     // asynchronous call (device film, no stats): return once the work is
     // enqueued on the scene's stream, as a stream-ordered library op does
     if (async_call(flags, stats)) return MH_OK;
-    if (!stats && !getenv("MH_VW_DEBUG")) {  // nothing to read back: the call's own sync + the bounds word
+    if (!stats && !vw_debug) {  // nothing to read back: the call's own sync + the bounds word
         MH_WAIT(s, flags, st);
         return check_bounds_counter(s, "mh_render");
     }
@@ -1071,7 +1077,7 @@ static int render_impl(mh_scene *s, const mh_integrator *in, uint32_t seed, uint
     unsigned long long iv[2] = {0, 0};  // [kCtrInvalid], [kCtrBounds]
     static_assert(kCtrBounds == kCtrInvalid + 1, "one read-back of both words");
     MH_HIP(hipMemcpyAsync(iv, invalid, sizeof(iv), hipMemcpyDeviceToHost, st));
-    if (volwave && vol_sched_mode())
+    if (sched)
         MH_HIP(hipMemcpyAsync(&n_lookups, s->counters.as<unsigned long long>() + kCtrLookups, 8,
                               hipMemcpyDeviceToHost, st));
     MH_WAIT(s, flags, st);  // the stats counters are read back
@@ -1088,7 +1094,7 @@ static int render_impl(mh_scene *s, const mh_integrator *in, uint32_t seed, uint
         MH_HIP(hipEventElapsedTime(&ms, ev[1], ev[ev_per_chunk - 1]));
         splat_ms += ms;
         // the fused bounce kernels are timed as one span (launch_wavefront_pass)
-        const uint32_t pairs = wavefront ? (wf_fused(s->S) || L.n_passes > 1 ? 1u : n_bounces) : 0u;
+        const uint32_t pairs = wavefront ? (facts.wf_fused || L.n_passes > 1 ? 1u : n_bounces) : 0u;
         for (uint32_t b = 0; b < pairs; ++b) {
             MH_HIP(hipEventElapsedTime(&ms, ev[2 + 2 * b], ev[3 + 2 * b]));
             trace_ms += ms;
@@ -1105,9 +1111,9 @@ static int render_impl(mh_scene *s, const mh_integrator *in, uint32_t seed, uint
                         ctr[1] += wctr[o + 1];
                     }
     }
-    if (volwave && vol_sched_mode() && getenv("MH_VW_DEBUG"))  // MH_EXP_VSCNT builds: wave trips per phase
+    if (sched && vw_debug)  // MH_EXP_VSCNT builds: wave trips per phase
         if (int rc2 = print_vs_phases(s)) return rc2;
-    if (volwave && !vol_sched_mode() && getenv("MH_VW_DEBUG")) {  // per-round queue sizes (+ MH_EXP_VWCNT builds: trips / steps)
+    if (volwave && !sched && vw_debug) {  // per-round queue sizes (+ MH_EXP_VWCNT builds: trips / steps)
         const uint32_t R = vw_rounds(*in), W = vw_counter_words(R) / (R + 1);
         std::vector<uint32_t> c((size_t)W * (R + 1));
         MH_HIP(hipMemcpy(c.data(), s->wf_ctr.ptr, c.size() * 4, hipMemcpyDeviceToHost));
@@ -1133,10 +1139,9 @@ static int render_impl(mh_scene *s, const mh_integrator *in, uint32_t seed, uint
         stats->ms_total = now_ms() - t_start;
         stats->ms_kernel = kernel_ms;
         // volpath on the phase scheduler: its k_vol_sched launches (one per chunk)
-        const bool sched = volwave && vol_sched_mode();
         stats->ms_trace = sched ? kernel_ms : trace_ms;
         stats->n_trace_launches = wavefront ? (uint64_t)n_chunks * n_bounces * L.n_passes : sched ? n_chunks : 0;
-        stats->mode = wavefront ? (wf_fused(s->S) ? 2u : 1u) : volwave ? 3u : 0u;
+        stats->mode = plan.mode;
         stats->invalid_samples = (uint32_t)std::min<unsigned long long>(n_invalid, 0xffffffffull);
         stats->grid_lookups = n_lookups;
         stats->aux_items = n_px * per_pixel;
@@ -1171,29 +1176,23 @@ int mh_render_samples(mh_scene *s, const mh_integrator *in, uint32_t seed, uint3
     MH_HIP(hipMemsetAsync(s->counters.ptr, 0, 256, st));
     LaneMap lm = lane_map(L, 0);
     if ((flags & MH_FLAG_WAVEFRONT) && vs_supported(s->S, *in) && vol_sched_mode()) {
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device);
-        MH_HIP(launch_vol_sched(s->S, *in, lm, s->S.sampler_seed + seed, n, n, dst, vs_blocks(cus),
+        MH_HIP(launch_vol_sched(s->S, *in, lm, s->S.sampler_seed + seed, n, n, dst, vs_blocks(device_cus(s->device)),
                                 s->counters.as<unsigned long long>(), st, alpha));
     } else if ((flags & MH_FLAG_WAVEFRONT) && vw_supported(s->S, *in)) {
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device);
         MH_HIP(s->wf_ws.alloc(vw_workspace_bytes(n)));
         MH_HIP(s->wf_ctr.alloc((size_t)vw_counter_words(vw_rounds(*in)) * 4));
         MH_HIP(launch_volwave(s->S, *in, lm, s->S.sampler_seed + seed, n, n, dst, s->wf_ws.ptr, n,
-                              s->wf_ctr.as<uint32_t>(), vw_blocks(cus), s->counters.as<unsigned long long>(), st,
-                              alpha));
+                              s->wf_ctr.as<uint32_t>(), vw_blocks(device_cus(s->device)),
+                              s->counters.as<unsigned long long>(), st, alpha));
     } else if (flags & MH_FLAG_WAVEFRONT) {
         if (in->type != MH_INTEGRATOR_PATH || in->max_depth > 64)
             return set_error(MH_ERR_UNSUPPORTED, "mh_render_samples: wavefront mode needs 'path' (max_depth <= 64) "
                                                  "or 'volpath' (max_depth <= 1024)");
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device);
         MH_HIP(s->wf_ws.alloc(wf_workspace_bytes(n)));
         MH_HIP(s->wf_ctr.alloc(std::max<size_t>(16, 4 * (size_t)wf_counter_words(in->max_depth))));
         MH_HIP(launch_wavefront(s->S, *in, lm, s->S.sampler_seed + seed, n, n, dst, s->wf_ws.ptr, n,
-                                s->wf_ctr.as<uint32_t>(), in->max_depth, wf_blocks(cus), nullptr, st, 1, nullptr,
-                                alpha));
+                                s->wf_ctr.as<uint32_t>(), in->max_depth, wf_blocks(device_cus(s->device)), nullptr,
+                                st, 1, nullptr, alpha));
     } else {
         MH_HIP(launch_render(s->S, *in, lm, s->S.sampler_seed + seed, 1, n, n, dst,
                              s->counters.as<unsigned long long>(), st, alpha));
@@ -1247,12 +1246,11 @@ static int prb_weights_impl(mh_scene *s, uint32_t seed, uint32_t spp, uint32_t s
         w = s->weights_tmp.as<float>();
     }
     if (!(flags & MH_FLAG_ACCUMULATE)) MH_HIP(hipMemsetAsync(w, 0, n_px * 4, st));
-    const bool fast = L.spp_pp >= 4 && s->S.rfilter == MH_RFILTER_GAUSSIAN &&
-                      s->S.rfilter_radius > 1.5f && s->S.rfilter_radius <= 2.5f;
     LaneMap lm = lane_map(L, 0);
     const uint32_t S_ = L.s_end - L.s_begin;
-    MH_SPLAT(s->S, lm, kSplatWeights, fast, (uint32_t)n_px, 1, n_px * S_, 0, nullptr, w, s->S.sampler_seed + seed,
-             L.spp_pp >= 4, st, nullptr, deterministic(flags), 0, n_px, nullptr);
+    MH_SPLAT(s->S, lm, kSplatWeights, fast_splat(L, s->S), (uint32_t)n_px, 1, n_px * S_, 0, nullptr, w,
+             s->S.sampler_seed + seed, L.spp_pp >= 4, st, nullptr, plan::deterministic(flags, env::deterministic()),
+             0, n_px, nullptr);
     if (int rc = reduce_result(s, flags, w, n_px, st, false)) return rc;
     if (!(flags & MH_FLAG_DEVICE_POINTERS))
         MH_HIP(hipMemcpyAsync(weights, w, n_px * 4, hipMemcpyDeviceToHost, st));
@@ -1358,9 +1356,8 @@ static hipError_t upload_slots(mh_scene *s, Slots &P, hipStream_t st, std::vecto
     bufs.assign(kMaxParams, nullptr);
     for (int k = 0; k < kMaxParams; ++k) bufs[k] = P.counts[k] ? s->tmp_c.as<float>() + off[k] : nullptr;
     P.corner.assign(kMaxParams, nullptr);
-    const char *ec = getenv("MH_GRID_CORNER");
     P.fx = false;
-    if (corners && (fx || !(ec && !strcmp(ec, "0")))) {
+    if (corners && (fx || !env::grid_corner_off())) {
         std::vector<size_t> coff(kMaxParams, 0);
         std::vector<bool> use(kMaxParams, false);
         size_t cfl = 0;
@@ -1466,23 +1463,42 @@ static int render_backward_impl(mh_scene *s, const mh_integrator *in, uint32_t s
     if (rc_slots) return rc_slots;
     std::vector<float *> bufs;
     GradArgs ga;
-    // MH_FLAG_DETERMINISTIC on prbvolpath: the grid gradient and the small
-    // slots in int64 fixed point (two passes, see the prbvolpath branch below)
-    const bool fx = vol && deterministic(flags);  // also the small slots (acc_add_fx)
+    const std::vector<size_t> &counts = P.counts;
+    const std::vector<uint32_t> &slot_of_param = P.slot_of_param;
+    const uint32_t n_rgb = P.n_rgb, n_bmp = P.n_bmp;
+    const uint32_t S_ = L.s_end - L.s_begin;
+    // ---- the plan (mh_plan.hpp): engine, determinism, chunks and streams ----
+    plan::Facts facts = call_facts(s, *in, flags, n_px, S_);
+    facts.n_rgb = n_rgb;
+    facts.n_bmp = n_bmp;
+    facts.bmp_slot_bytes = (uint64_t)counts[kMaxRgbParams] * 4;
+    // (several bitmaps: all with the same channel count, as the scatter's
+    // transposed issue assumes)
+    {
+        uint32_t ch = 0;
+        for (uint32_t t = 0; t < (uint32_t)P.slot_of_tex.size(); ++t)
+            if (P.slot_of_tex[t] >= kMaxRgbParams) {
+                const uint32_t c = s->h_textures[t].channels;
+                facts.bmp_same_ch = facts.bmp_same_ch && (ch == 0 || ch == c);
+                ch = c;
+            }
+    }
+    const plan::BackwardPlan plan =
+        plan::plan_backward(facts, env::plan_env(vol ? env::Call::BackwardVol : env::Call::Backward));
+    const bool fused = plan.fused, bmp_wf = plan.bmp_wf, wavefront = plan.wavefront;
+    // MH_FLAG_DETERMINISTIC on prbvolpath (fx) or on prb's replay kernel
+    // (det_replay): int64 fixed point in two passes
+    const bool fx = plan.fx, det_replay = plan.det_replay, fxr = plan.fxr;
     MH_HIP(upload_slots(s, P, st, bufs, ga, vol, fx));
     if (fx)
         for (int k = 0; k < kMaxParams; ++k)
             if (P.grid_res[k][0] && !P.corner[k])
                 return set_error(MH_ERR_OUT_OF_MEMORY,
                                  "render_backward(): the deterministic grid gradient's corner block could not be allocated");
-    const std::vector<size_t> &counts = P.counts;
-    const std::vector<uint32_t> &slot_of_param = P.slot_of_param;
-    const uint32_t n_rgb = P.n_rgb, n_bmp = P.n_bmp, bmp_tex = P.bmp_tex;
     // one bitmap parameter of <= 48 KiB: the replay kernel accumulates its
     // texel gradients per workgroup in LDS (k_prb_backward)
     // (MH_PRB_LDS_TEX=0: global atomics, the parity tests' cross-check)
-    const char *env_lds = getenv("MH_PRB_LDS_TEX");
-    if (n_bmp == 1 && counts[kMaxRgbParams] * 4 <= (48u << 10) && !(env_lds && !strcmp(env_lds, "0"))) {
+    if (plan.lds_tex) {
         ga.lds_slot = kMaxRgbParams;
         ga.lds_floats = (uint32_t)counts[kMaxRgbParams];
     }
@@ -1498,8 +1514,6 @@ static int render_backward_impl(mh_scene *s, const mh_integrator *in, uint32_t s
     if (!weights) {
         MH_HIP(s->weights_tmp.alloc(n_px * 4));
         MH_HIP(hipMemsetAsync(s->weights_tmp.ptr, 0, n_px * 4, st));
-        const bool fast = L.spp_pp >= 4 && s->S.rfilter == MH_RFILTER_GAUSSIAN &&
-                          s->S.rfilter_radius > 1.5f && s->S.rfilter_radius <= 2.5f;
         // W of every sample of every pixel (common.py:936-947); with
         // MH_FLAG_REDUCE the slab's own samples + an all-reduce, unless each
         // rank is to compute the whole image itself (MH_FLAG_LOCAL_WEIGHTS)
@@ -1510,9 +1524,9 @@ static int render_backward_impl(mh_scene *s, const mh_integrator *in, uint32_t s
             Lall.s_end = L.spp_pp;
         }
         LaneMap lmw = lane_map(Lall, 0);
-        MH_SPLAT(s->S, lmw, kSplatWeights, fast, (uint32_t)n_px, 1, n_px * (Lall.s_end - Lall.s_begin), 0, nullptr,
-                 s->weights_tmp.as<float>(), s->S.sampler_seed + seed, L.spp_pp >= 4, st, nullptr,
-                 deterministic(flags), 0, n_px, nullptr);
+        MH_SPLAT(s->S, lmw, kSplatWeights, fast_splat(L, s->S), (uint32_t)n_px, 1,
+                 n_px * (Lall.s_end - Lall.s_begin), 0, nullptr, s->weights_tmp.as<float>(),
+                 s->S.sampler_seed + seed, L.spp_pp >= 4, st, nullptr, plan.determ, 0, n_px, nullptr);
         if (slab_w)
             if (int rc = reduce_result(s, flags, s->weights_tmp.as<float>(), n_px, st, false)) return rc;
         w = s->weights_tmp.as<float>();
@@ -1527,43 +1541,9 @@ static int render_backward_impl(mh_scene *s, const mh_integrator *in, uint32_t s
     MH_HIP(s->gw.alloc(n_px * 16));  // float4 per pixel (k_grad_over_w)
     MH_HIP(launch_grad_over_w(n_px, g_in, w, s->gw.as<float>(), st));
     g_in = s->gw.as<float>();
-    const uint32_t S_ = L.s_end - L.s_begin;
     const uint64_t n = n_px * S_;
-    // fused single traversal when every requested parameter is an rgb constant,
-    // unless the replay is forced (MH_FLAG_PRB_REPLAY / MH_PRB_REPLAY=1); the
-    // fused form runs as wavefront kernels unless MH_FLAG_MEGAKERNEL / MH_MODE=mega
-    const char *env_replay = getenv("MH_PRB_REPLAY");
-    const char *env_mode = getenv("MH_MODE");
-    const bool replay = (flags & MH_FLAG_PRB_REPLAY) || (env_replay && !strcmp(env_replay, "1"));
-    const bool mega = (flags & MH_FLAG_MEGAKERNEL) || (env_mode && !strcmp(env_mode, "mega"));
-    const bool fused = !vol && n_bmp == 0 && !replay;
-    // bitmap parameters: the fused PRB wavefront logs their vertices (with the
-    // bitmap's index) and a scatter pass charges the texels (WfBmp,
-    // mh_wavefront.hip) -- packet-engine scenes, max_depth <= 32
-    // (MH_PRB_BMP_WF=0: the replay megakernel)
-    const char *env_bwf = getenv("MH_PRB_BMP_WF");
-    const char *env_pvl = getenv("MH_PVP_NEE_LOG");  // 0: prbvolpath replays its NEE walks (no log)
-    // (several bitmaps: all with the same channel count, as the scatter's
-    // transposed issue assumes)
-    bool bmp_same_ch = true;
-    {
-        uint32_t ch = 0;
-        for (uint32_t t = 0; t < (uint32_t)P.slot_of_tex.size(); ++t)
-            if (P.slot_of_tex[t] >= kMaxRgbParams) {
-                const uint32_t c = s->h_textures[t].channels;
-                bmp_same_ch = bmp_same_ch && (ch == 0 || ch == c);
-                ch = c;
-            }
-    }
-    const bool bmp_wf = !vol && n_bmp >= 1 && bmp_same_ch && !replay && !mega && wf_fused(s->S) &&
-                        in->max_depth >= 1 && in->max_depth <= 32 && !(env_bwf && !strcmp(env_bwf, "0"));
-    const bool wavefront = ((fused && in->max_depth <= 64 && !mega) || bmp_wf);
-    // MH_FLAG_DETERMINISTIC on the replay kernel (bitmaps the wavefront cannot
-    // take, MH_FLAG_PRB_REPLAY, megakernel): the int64 two-pass form of
-    // prbvolpath -- small slots through acc_add_fx, bitmap texels through
-    // bmp_add_fx into an int64 mirror of the slot block (no LDS accumulator)
-    const bool det_replay = deterministic(flags) && !vol && !wavefront;
-    const bool fxr = fx || det_replay;
+    // the deterministic replay: small slots through acc_add_fx, bitmap texels
+    // through bmp_add_fx into an int64 mirror of the slot block (no LDS accumulator)
     if (det_replay) {
         size_t total = 0;
         for (int k = 0; k < kMaxParams; ++k) total += (counts[k] + 3) / 4 * 4;
@@ -1625,26 +1605,14 @@ static int render_backward_impl(mh_scene *s, const mh_integrator *in, uint32_t s
     };
     MH_HIP(hipEventRecord(s->ev0, st));
     if (wavefront) {
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device);
-        const char *ec = getenv("MH_WF_CHUNK");
-        uint64_t max_samples = std::min<uint64_t>(
-            wf_max_chunk(), ec ? std::max<uint64_t>(1024, strtoull(ec, nullptr, 10)) : wf_max_chunk());
-        const uint32_t n_depth = std::max<uint32_t>(1, in->max_depth - 1);
-        if (bmp_wf)  // vertex records: 48 B per path and depth; at most 8 GiB of them per chunk
-            max_samples = std::min<uint64_t>(max_samples, std::max<uint64_t>(1 << 16, (8ull << 30) / (48ull * n_depth)));
-        uint32_t chunk_px = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_px, max_samples / S_));
-        // two-stream chunk pipeline (fork_stream): float gradients only
-        // (per-stream block partials, atomic texel scatter)
-        const bool two_ok = !deterministic(flags) && !(flags & MH_FLAG_SHARED_DEVICE) && chunk_streams_enabled();
-        if (two_ok && chunk_px >= n_px && n_px >= 2 && n_px * S_ >= kTwoStreamMinSamples)
-            chunk_px = (uint32_t)((n_px + 1) / 2);
-        const bool two = two_ok && chunk_px < n_px;
+        const int cus = device_cus(s->device);
+        const uint32_t n_depth = plan.n_depth, chunk_px = plan.chunks.chunk_px;
+        const bool two = plan.chunks.two;  // two-stream chunk pipeline (fork_stream)
         // MH_FLAG_SHARED_DEVICE (another call runs beside this one) or the two
         // chunk streams: the launches take a share of the CUs' slots (wf_blocks)
         const uint32_t grid = wf_grid(wf_blocks(cus, two || (flags & MH_FLAG_SHARED_DEVICE) != 0));
         const uint64_t cap = (uint64_t)chunk_px * S_;
-        const size_t n_chunks = (size_t)((n_px + chunk_px - 1) / chunk_px);
+        const size_t n_chunks = (size_t)plan.chunks.n_chunks;
         const uint32_t n_bounces = in->max_depth;
         const size_t ctr_per_chunk = wf_counter_words(n_bounces);
         MH_HIP(s->wf_ws.alloc(wf_workspace_bytes(cap)));
@@ -1674,8 +1642,8 @@ static int render_backward_impl(mh_scene *s, const mh_integrator *in, uint32_t s
                 if (P.slot_of_tex[t] >= kMaxRgbParams) bmp.tex[P.slot_of_tex[t] - kMaxRgbParams] = t;
             bmp.grad = bufs[kMaxRgbParams];
             bmp.n_floats = (uint32_t)boff;
-            bmp.lds_max = (env_lds && !strcmp(env_lds, "0")) ? 0u : (uint32_t)std::min(max_wg, 64 << 10);
-            if (deterministic(flags)) {  // fixed-point texel sums (k_wf_bitmap_scatter<false, Fx>)
+            bmp.lds_max = plan.bmp_lds ? (uint32_t)std::min(max_wg, 64 << 10) : 0u;
+            if (plan.determ) {  // fixed-point texel sums (k_wf_bitmap_scatter<false, Fx>)
                 MH_HIP(s->bmp_fx.alloc((size_t)bmp.n_floats * 8 + 256));
                 bmp.fx_word = s->bmp_fx.as<uint32_t>();
                 bmp.fx_acc = reinterpret_cast<unsigned long long *>(s->bmp_fx.as<uint8_t>() + 256);
@@ -1687,7 +1655,7 @@ static int render_backward_impl(mh_scene *s, const mh_integrator *in, uint32_t s
         }
         // MH_FLAG_DETERMINISTIC: rgb slots summed per path and reduced in a
         // fixed order (WfDet); bitmap texels in int64 fixed point (bmp.fx_acc)
-        const bool det_grad = deterministic(flags) && n_rgb > 0;
+        const bool det_grad = plan.det_grad;
         if (det_grad) MH_HIP(s->wf_ws_det.alloc(wf_det_workspace_bytes(cap)));
         MH_HIP(s->wf_ctr.alloc(ctr_per_chunk * n_chunks * 4));
         const size_t partial_bytes = (size_t)grid * kMaxRgbParams * 3 * 4;
@@ -1728,19 +1696,16 @@ static int render_backward_impl(mh_scene *s, const mh_integrator *in, uint32_t s
         if (two) MH_HIP(launch_wf_grad_reduce(s->wf_partial2.as<float>(), grid, n_rgb, ga.bufs, st));
         wf_ctr_words = ctr_per_chunk;
         wf_chunks = n_chunks;
-    } else if (vol && !(env_pvl && !strcmp(env_pvl, "0"))) {
-        // prbvolpath: persistent grid, one NEE-walk log per thread (NeeLog)
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device);
-        const char *ecap = getenv("MH_PVP_NEE_CAP");  // tests: small logs exercise the replay fallback
-        // single pass (MainLog) unless MH_PVP_SINGLE=0; MH_PVP_MAIN_CAP: entries per thread
-        const char *esp = getenv("MH_PVP_SINGLE"), *emc = getenv("MH_PVP_MAIN_CAP");
-        uint32_t main_cap = (esp && !strcmp(esp, "0")) ? 0u : emc ? (uint32_t)std::max(1, atoi(emc)) : kPvpMainCap;
-        const uint32_t cap = ecap ? (uint32_t)std::max(1, atoi(ecap)) : kPvpNeeCap;
-        // the single pass runs on the phase scheduler (k_vol_sched<PvBwdMachine>)
+    } else if (plan.pvp_log) {
+        // prbvolpath: persistent grid, one NEE-walk log per thread (NeeLog;
+        // MH_PVP_NEE_LOG=0: the NEE walks are replayed, the branches below);
+        // single pass (MainLog, main_cap entries per thread) unless
+        // MH_PVP_SINGLE=0, on the phase scheduler (k_vol_sched<PvBwdMachine>)
         // unless MH_PVP_SCHED=0 (the per-sample kernel k_prbvol_backward)
-        const char *esc = getenv("MH_PVP_SCHED");
-        bool sched = main_cap && vs_supported(s->S, *in) && !(esc && !strcmp(esc, "0"));
+        const int cus = device_cus(s->device);
+        uint32_t main_cap = plan.main_cap;
+        const uint32_t cap = plan.nee_cap;
+        bool sched = plan.sched;
         // the persistent grid (and with it both per-thread logs): the
         // scheduler's, or k_prbvol_backward's shrunk to the work (a wave takes
         // 64 samples per batch, so more threads than samples would only hold log space)
@@ -1792,7 +1757,7 @@ static int render_backward_impl(mh_scene *s, const mh_integrator *in, uint32_t s
                                         s->counters.as<unsigned long long>(), st));
             MH_HIP(launch_vol_sched_bwd_replays(s->S, *in, lm0, s->S.sampler_seed + seed, n, bw,
                                                 s->counters.as<unsigned long long>(), st));
-            if (getenv("MH_VW_DEBUG")) {
+            if (env::vw_debug()) {
                 MH_WAIT(s, flags, st);
                 if (int rc2 = print_vs_phases(s)) return rc2;
                 uint32_t oc[3];
@@ -1954,49 +1919,34 @@ static int render_forward_impl(mh_scene *s, const mh_integrator *in, uint32_t se
         MH_HIP(hipMemcpyAsync(bufs[slot], tangents[k], P.counts[slot] * 4,
                               dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     }
-    // the film: as mh_render (RGBW, or RGBW + an alpha plane gathered into R G B A W)
+    // the film: as mh_render
     const uint64_t n_px = (uint64_t)L.W * L.H;
-    const bool alpha = has_alpha(s->pixel_format);
-    const size_t film_bytes = n_px * (alpha ? 20 : 16);
-    float *film = film_rgbw;
-    if (!dev) {
-        MH_HIP(s->film_tmp.alloc(film_bytes));
-        film = s->film_tmp.as<float>();
-    }
-    if (!(flags & MH_FLAG_ACCUMULATE)) MH_HIP(hipMemsetAsync(film, 0, film_bytes, st));
-    else if (!dev) MH_HIP(hipMemcpyAsync(film, film_rgbw, film_bytes, hipMemcpyHostToDevice, st));
-    float *film4 = film, *film_a = nullptr;
-    if (alpha) {
-        MH_HIP(s->film4.alloc(n_px * 16));
-        MH_HIP(s->alpha_px.alloc(n_px * 4));
-        film4 = s->film4.as<float>();
-        film_a = s->alpha_px.as<float>();
-        MH_HIP(hipMemsetAsync(film4, 0, n_px * 16, st));
-        MH_HIP(hipMemsetAsync(film_a, 0, n_px * 4, st));
-    }
+    FilmStage F;
+    if (int rc2 = stage_film(s, n_px, film_rgbw, flags, st, F)) return rc2;
+    const bool alpha = F.alpha;
+    const size_t film_bytes = F.bytes;
+    float *const film = F.film, *const film4 = F.film4, *const film_a = F.film_a;
     MH_HIP(hipMemsetAsync(s->counters.ptr, 0, 256, st));
     const uint32_t S_ = L.s_end - L.s_begin;
-    const uint32_t chunk_px = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_px, wf_max_chunk() / S_));
-    const uint64_t plane = (uint64_t)chunk_px * S_;
-    MH_HIP(s->work.alloc(plane * (alpha ? 6 : 5) * sizeof(float)));
     // prb on packet-engine scenes: the fused forward-mode wavefront
     // (k_wf_bounce_fwd); prbvolpath, larger scenes or MH_FLAG_MEGAKERNEL /
     // MH_MODE=mega: the per-sample kernel (k_render_forward)
-    const char *env_mode = getenv("MH_MODE");
-    const bool wavefront = in->type == MH_INTEGRATOR_PRB && wf_fused(s->S) && in->max_depth >= 1 &&
-                           in->max_depth <= 64 && !(flags & MH_FLAG_MEGAKERNEL) && !(env_mode && !strcmp(env_mode, "mega"));
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device);
+    const plan::ForwardPlan plan =
+        plan::plan_forward(call_facts(s, *in, flags, n_px, S_), env::plan_env(env::Call::Forward));
+    const uint32_t chunk_px = plan.chunk_px;
+    const uint64_t plane = (uint64_t)chunk_px * S_;
+    MH_HIP(s->work.alloc(plane * (alpha ? 6 : 5) * sizeof(float)));
+    const bool wavefront = plan.wavefront;
+    const int cus = device_cus(s->device);
     if (wavefront) {
         MH_HIP(s->wf_ws.alloc(wf_workspace_bytes(plane)));
         MH_HIP(s->wf_ws_prb.alloc(wf_prb_workspace_bytes(plane)));
         MH_HIP(s->wf_ctr.alloc((size_t)wf_counter_words(in->max_depth) * 4));
     }
-    const bool fast_splat = L.spp_pp >= 4 && s->S.rfilter == MH_RFILTER_GAUSSIAN && s->S.rfilter_radius > 1.5f &&
-                            s->S.rfilter_radius <= 2.5f;
+    const bool fast = fast_splat(L, s->S);
     const int coalesce = L.spp_pp >= 4;  // block.set_coalesce(... and spp >= 4) (common.py:795-796)
     const uint32_t seed_value = s->S.sampler_seed + seed;
-    const bool determ = deterministic(flags);
+    const bool determ = plan.determ;
     unsigned long long *bounds = s->counters.as<unsigned long long>() + kCtrBounds;
     MH_HIP(hipEventRecord(s->ev0, st));
     for (uint64_t p0 = 0; p0 < n_px; p0 += chunk_px) {
@@ -2012,10 +1962,10 @@ static int render_forward_impl(mh_scene *s, const mh_integrator *in, uint32_t se
             MH_HIP(launch_render_forward(s->S, *in, lm, seed_value, n, plane, s->work.as<float>(), ga,
                                          s->counters.as<unsigned long long>(), st, alpha));
         // no sample check here: tangent radiance is legitimately negative
-        MH_SPLAT(s->S, lm, kSplatFilm, fast_splat, npx, 1, n, plane, s->work.as<float>(), film4, seed_value,
+        MH_SPLAT(s->S, lm, kSplatFilm, fast, npx, 1, n, plane, s->work.as<float>(), film4, seed_value,
                  coalesce, st, nullptr, determ, s->work.bytes / 4, n_px * 4, bounds);
         if (alpha)
-            MH_SPLAT(s->S, lm, kSplatAlpha, fast_splat, npx, 1, n, plane, s->work.as<float>(), film_a, seed_value,
+            MH_SPLAT(s->S, lm, kSplatAlpha, fast, npx, 1, n, plane, s->work.as<float>(), film_a, seed_value,
                      coalesce, st, nullptr, determ, s->work.bytes / 4, n_px, bounds);
     }
     if (alpha) MH_HIP(launch_film_rgbaw(n_px, film4, film_a, film, st));
@@ -2042,7 +1992,7 @@ static int render_forward_impl(mh_scene *s, const mh_integrator *in, uint32_t se
         stats->ms_kernel = ms;
         stats->ms_trace = 0.f;
         stats->n_trace_launches = 0;
-        stats->mode = wavefront ? 2u : 0u;  // fused wavefront / per-sample kernel
+        stats->mode = plan.mode;  // 2: fused wavefront, 0: per-sample kernel
         stats->invalid_samples = 0;  // not counted: a tangent's radiance may be negative
     }
     return MH_OK;
@@ -2078,9 +2028,7 @@ static int trace_impl(mh_scene *s, bool shadow, uint64_t n, const float *rays, f
         doc = reinterpret_cast<uint32_t *>(base);
     }
     // persistent grid: 8 workgroups of 256 lanes per CU
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device);
-    uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)cus * 8);
+    uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)device_cus(s->device) * 8);
     MH_HIP(hipEventRecord(s->ev0, st));
     MH_HIP(launch_trace(s->S, shadow, n, r, dt, du, dv, dp, ds, di, doc, grid, st));
     MH_HIP(hipEventRecord(s->ev1, st));

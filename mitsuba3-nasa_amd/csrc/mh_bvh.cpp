@@ -16,6 +16,7 @@
 #include <thread>
 
 #include "mh_device.hpp"
+#include "mh_env.hpp"
 #include "mh_internal.hpp"
 
 namespace mh {
@@ -283,9 +284,8 @@ struct Builder {
 
 // build threads: MH_BVH_THREADS, else the host's cores (at most 32)
 uint32_t bvh_threads() {
-    if (const char *e = getenv("MH_BVH_THREADS")) return (uint32_t)std::max(1, atoi(e));
     const uint32_t hc = std::thread::hardware_concurrency();
-    return std::max(1u, std::min(32u, hc ? hc : 1u));
+    return (uint32_t)env::bvh_threads((int)std::max(1u, std::min(32u, hc ? hc : 1u)));
 }
 
 }  // namespace

@@ -24,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "mh_env.hpp"
 #include "mh_internal.hpp"
 #include "../../include/mitsuba_hip.h"
 
@@ -241,10 +242,7 @@ void comm_abort(mh_comm *c) {
 }
 
 int comm_wait(mh_comm *c, hipStream_t st, const char *api) {
-    static const double timeout_s = [] {
-        const char *e = getenv("MH_COMM_TIMEOUT_S");
-        return e ? std::max(0.001, atof(e)) : 1800.0;
-    }();
+    static const double timeout_s = mh::env::comm_timeout_s(1800.0);
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t it = 0;; ++it) {
         const hipError_t q = hipStreamQuery(st);
@@ -285,7 +283,7 @@ int comm_reduce_one(mh_comm *c, int device, float *buf, uint64_t count, hipStrea
     // test hook (tests/test_gpu_comm.py): a one-rank sum leaves the data as it
     // is, so a wrong extent, buffer or root would go unseen; MH_TEST_COMM_SCALE
     // doubles exactly the reduced extent (buf += buf) at world size 1
-    if (rc == MH_OK && c->nranks == 1 && count && getenv("MH_TEST_COMM_SCALE"))
+    if (rc == MH_OK && c->nranks == 1 && count && mh::env::test_comm_scale())
         if (mh::launch_accumulate(buf, buf, count, st) != hipSuccess)
             rc = mh_report_error(MH_ERR_HIP, "MH_TEST_COMM_SCALE: launch failed");
     return rc;

@@ -45,6 +45,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "mh_env.hpp"
 #include "mh_internal.hpp"
 #include "mh_shading.hpp"
 
@@ -1839,15 +1840,16 @@ k_vol_sched(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value, uin
 // ---------------------------------------------------------------------------
 // volpath execution: phase-scheduled persistent kernel (default) or
 // main / walk rounds (MH_VOL_MODE=rounds)
-bool vol_sched_mode() {
-    const char *e = getenv("MH_VOL_MODE");
-    return !(e && !strcmp(e, "rounds"));
+bool vol_sched_mode() { return !env::vol_mode_rounds(); }
+// one resident round of 256-lane workgroups (a wave per SIMD each)
+uint32_t vs_blocks(int cus) { return (uint32_t)cus * (uint32_t)env::vs_bpc(MH_VS_WAVES); }
+// the traversal engine of a launch: wave-coherent packets for scenes with pair
+// records (MH_TRAVERSAL=lane: per-lane)
+static bool vol_packet(const DScene &S) {
+    return S.n_prims > 0 && S.n_prims <= wf_packet_max_prims() && !env::traversal_lane();
 }
-uint32_t vs_blocks(int cus) {
-    uint32_t bpc = MH_VS_WAVES;  // one resident round of 256-lane workgroups (a wave per SIMD each)
-    if (const char *e = getenv("MH_VS_BPC")) bpc = std::max(1, atoi(e));
-    return (uint32_t)cus * bpc;
-}
+// the phase scheduler's LDS shading tables
+static bool vs_tables(const DScene &S) { return S.tab_bytes != 0 && !env::vs_notab(); }
 uint64_t vw_max_chunk() { return 1ull << 23; }
 size_t vw_workspace_bytes(uint64_t cap) { return (size_t)2 * kVwPlanes * 16 * cap; }
 uint32_t vw_counter_words(uint32_t rounds) { return kVwCtr * (rounds + 1); }
@@ -1862,9 +1864,7 @@ bool vs_supported(const DScene &S, const IntegratorParams &in) {
            S.n_media < 255;
 }
 uint32_t vw_blocks(int cus) {
-    uint32_t bpc = 8;
-    if (const char *e = getenv("MH_VW_BPC")) bpc = std::max(1, atoi(e));
-    return std::max<uint32_t>(kVwSeg, (uint32_t)cus * bpc / kVwSeg * kVwSeg);
+    return std::max<uint32_t>(kVwSeg, (uint32_t)cus * (uint32_t)env::vw_bpc(8) / kVwSeg * kVwSeg);
 }
 
 hipError_t launch_vol_sched(const DScene &S, const IntegratorParams &in, const LaneMap &lm, uint32_t seed_value,
@@ -1873,9 +1873,7 @@ hipError_t launch_vol_sched(const DScene &S, const IntegratorParams &in, const L
     if (n == 0) return hipSuccess;
     const size_t sh = lds_bytes(S, 256);
     const bool lds = S.lds_bytes_bvh != 0;
-    const char *te = getenv("MH_TRAVERSAL");
-    const bool pk = S.n_prims > 0 && S.n_prims <= wf_packet_max_prims() && !(te && !strcmp(te, "lane"));
-    const bool tab = S.tab_bytes != 0 && !getenv("MH_VS_NOTAB");
+    const bool pk = vol_packet(S), tab = vs_tables(S);
 #define MH_VS1(Mc, L, P, T)                                                                                   \
     hipLaunchKernelGGL((k_vol_sched<Mc, L, P, T>), dim3(grid), dim3(256), sh + (T ? vs_tab_bytes(S) : 0u) + (P ? vs_defer_bytes(S) : 0u), st, S, \
                        in, lm, seed_value, n, plane, out, counters, work, alpha, VsBwdArgs{})
@@ -1942,9 +1940,7 @@ hipError_t launch_vol_sched_bwd(const DScene &S, const IntegratorParams &in, con
         return hipErrorInvalidValue;
     const size_t sh = lds_bytes(S, 256);
     const bool lds = S.lds_bytes_bvh != 0;
-    const char *te = getenv("MH_TRAVERSAL");
-    const bool pk = S.n_prims > 0 && S.n_prims <= wf_packet_max_prims() && !(te && !strcmp(te, "lane"));
-    const bool tab = S.tab_bytes != 0 && !getenv("MH_VS_NOTAB");
+    const bool pk = vol_packet(S), tab = vs_tables(S);
     unsigned long long *work = counters + 32;  // the 8 queue heads of this launch (128 B apart)
     hipError_t e = hipMemsetAsync(work, 0, 8 * 128, st);
     if (e != hipSuccess) return e;
@@ -2064,12 +2060,9 @@ hipError_t launch_volwave(const DScene &S, const IntegratorParams &in, const Lan
     const uint32_t seg_cap = (uint32_t)((n + kVwSeg - 1) / kVwSeg);
     const size_t sh = lds_bytes(S, 256);
     const bool lds = S.lds_bytes_bvh != 0;
-    // packet engine for scenes with pair records (MH_TRAVERSAL=lane: per-lane)
-    const char *te = getenv("MH_TRAVERSAL");
-    const bool pk = S.n_prims > 0 && S.n_prims <= wf_packet_max_prims() && !(te && !strcmp(te, "lane"));
+    const bool pk = vol_packet(S);
     // main / walk rounds while many paths are live, then one finish launch
-    uint32_t wave_rounds = kVwWaveRounds;
-    if (const char *e = getenv("MH_VW_ROUNDS")) wave_rounds = (uint32_t)std::max(1, atoi(e));
+    const uint32_t wave_rounds = (uint32_t)env::vw_rounds((int)kVwWaveRounds);
     for (uint32_t r = 0; r < rounds; ++r) {
         const VwPlanes &c = side[r & 1], &x = side[(r + 1) & 1];
         const uint32_t *cin = ctr + (size_t)kVwCtr * r;

@@ -23,6 +23,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "mh_env.hpp"
 #include "mh_shading.hpp"
 
 namespace mh {
@@ -78,24 +79,15 @@ constexpr uint32_t kMaxWfBounces = (1u << (32 - kPidBits)) - 1u;
 constexpr uint32_t kPacketMaxPrims = 64;
 // MH_PACKET_MAX_PRIMS: experiments with larger packet scenes (read once)
 uint32_t wf_packet_max_prims() {
-    static const uint32_t v = [] {
-        const char *e = getenv("MH_PACKET_MAX_PRIMS");
-        return e ? (uint32_t)std::max(1, atoi(e)) : kPacketMaxPrims;
-    }();
+    static const uint32_t v = (uint32_t)env::packet_max_prims((int)kPacketMaxPrims);
     return v;
 }
 static bool use_packet(const DScene &S) {
-    const char *e = getenv("MH_TRAVERSAL");
     if (S.n_prims > wf_packet_max_prims()) return false;  // no pair records beyond (mh_api.hip)
-    if (e && !strcmp(e, "packet")) return true;
-    if (e && !strcmp(e, "lane")) return false;
-    return true;
+    return !env::traversal_lane();
 }
 // MH_WF_FUSED=0 keeps the three-kernel pipeline (trace / shade / shadow)
-static bool wf_unfused() {
-    const char *e = getenv("MH_WF_FUSED");
-    return e && !strcmp(e, "0");
-}
+static bool wf_unfused() { return env::wf_unfused(); }
 // the stream kernels are instantiated per node format (Eng), so each one's
 // register allocation is that of its own traversal engine
 #define MH_WF_DISPATCH(K, ...)                                                                        \
@@ -2299,9 +2291,8 @@ uint32_t wf_grid(uint32_t grid) { return std::max<uint32_t>(kSeg, grid / kSeg * 
 // 30 -> 2,074-2,094, 20 -> 2,098-2,106, 12 -> 2,105-2,129, 8 -> 2,105-2,117,
 // 6 -> 2,070-2,082 Msamples/s (alone, 12 would cost 6 %: 1,824 vs 1,946)
 uint32_t wf_blocks(int cus, bool shared) {
-    uint32_t bpc = shared ? 12 : 30;  // measured alone: 8 -> 54.6, 20 -> 51.4, 30 -> 51.2, 60 -> 52.3 ms per bench step
-    if (const char *e = getenv("MH_WF_BPC")) bpc = std::max(1, atoi(e));
-    return (uint32_t)cus * bpc;
+    // measured alone: 8 -> 54.6, 20 -> 51.4, 30 -> 51.2, 60 -> 52.3 ms per bench step
+    return (uint32_t)cus * (uint32_t)env::wf_bpc(shared ? 12 : 30);
 }
 
 hipError_t launch_wf_grad_reduce(const float *partial, uint32_t grid, uint32_t n_rgb, float *const *bufs,
