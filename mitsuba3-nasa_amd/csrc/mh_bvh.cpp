@@ -2,8 +2,24 @@
 // build of the reference (src/render/scene_optix.inl:449-514).
 //
 // Output layout is the device layout of mh_device.hpp: 64-B nodes holding the
-// two child boxes (padded conservatively so the fma slab test can never
-// reject a true hit) and 64-B primitive records in leaf order.
+// two child boxes and 64-B primitive records in leaf order.
+//
+// Culling is conservative in two parts.  The boxes are padded here
+// (Builder::pad) by 1e-5 of their coordinates and extent, which covers the
+// fma slab test's rounding wherever the box's coordinates are at least 0.02
+// of the ray origin's.  Where they are not (a small box near the world's
+// origin seen from far away), the rounding of o * inv exceeds any padding of
+// the box, and the device widens the slab interval by a relative slack
+// instead (mh_shading.hpp kSlabSlack): before that slack a millimetre-sized
+// mesh at the world's origin lost up to 5 % of the rays aimed at its vertices
+// from 50 units away.  Together they keep a box test from rejecting a
+// primitive whose exact hit point lies in the (unpadded) box, whatever the
+// origin.  What remains outside: the tests compare against the float32 hit
+// distance of the primitive tests, so a hit whose float32 distance is off by
+// more than 2^-21 of itself (grazing incidence on a plane seen from far away)
+// can still resolve differently from a brute force over all primitives.
+// tests/test_gpu_trace_edges.py pins every engine on rays built to sit on
+// these edges.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

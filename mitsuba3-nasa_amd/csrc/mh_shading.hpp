@@ -75,7 +75,24 @@ MH_DEV bool closer(float tt, const Prim &p, const Hit &hit) {
     return (tt < hit.t) | ((tt == hit.t) & (p.info.w < hit.key));
 }
 
-// Slab test for both children; conservative (host pads every box).
+// The ray's share of the slab tests' rounding.  A slab position is computed
+// as fma(bound, inv, -ood) with ood = o * inv rounded to float, so it carries
+// up to 2^-24 (3 |o| + 2 |bound|) |inv| of error: the reciprocal, the product
+// o * inv and the fma.  The host pads every box by at least 1e-5 |bound|
+// (mh_bvh.cpp Builder::pad), which is more than that error as long as
+// |bound| >= 0.02 |o|.  Below that -- a small box near the world's origin
+// seen from far away, where an ulp of the origin exceeds the padding -- the
+// slab position is (bound - o) inv with |bound - o| >= 0.98 |o|, so the error
+// is at most 3.1 * 2^-24 of the position itself: there a relative slack
+// covers it, and no padding of the box can.  Entry distances are clamped at
+// 0, so widening every exit by (1 + 2^-21) and narrowing every entry by the
+// same share is the single factor below on the smallest exit; 2^-20 leaves
+// the other half to the rounding of the hit distance the exit is clamped to
+// (maxt, or the float32 t of the best hit so far).
+constexpr float kSlabSlack = 1.f + 0x1p-20f;
+
+// Slab test for both children; conservative in the box (the host's padding)
+// and in the ray (kSlabSlack).
 MH_DEV void box2(const Node &n, V3 inv, V3 ood, float tmax, bool &h0, bool &h1, float &t0,
                  float &t1) {
     float a0 = __builtin_fmaf(n.lo0.x, inv.x, -ood.x), b0 = __builtin_fmaf(n.hi0.x, inv.x, -ood.x);
@@ -83,14 +100,14 @@ MH_DEV void box2(const Node &n, V3 inv, V3 ood, float tmax, bool &h0, bool &h1, 
     float a2 = __builtin_fmaf(n.lo0.z, inv.z, -ood.z), b2 = __builtin_fmaf(n.hi0.z, inv.z, -ood.z);
     float lo = fmaxf(fmaxf(fminf(a0, b0), fminf(a1, b1)), fmaxf(fminf(a2, b2), 0.f));
     float hi = fminf(fminf(fmaxf(a0, b0), fmaxf(a1, b1)), fminf(fmaxf(a2, b2), tmax));
-    h0 = lo <= hi;
+    h0 = lo <= hi * kSlabSlack;
     t0 = lo;
     a0 = __builtin_fmaf(n.lo1.x, inv.x, -ood.x); b0 = __builtin_fmaf(n.hi1.x, inv.x, -ood.x);
     a1 = __builtin_fmaf(n.lo1.y, inv.y, -ood.y); b1 = __builtin_fmaf(n.hi1.y, inv.y, -ood.y);
     a2 = __builtin_fmaf(n.lo1.z, inv.z, -ood.z); b2 = __builtin_fmaf(n.hi1.z, inv.z, -ood.z);
     lo = fmaxf(fmaxf(fminf(a0, b0), fminf(a1, b1)), fmaxf(fminf(a2, b2), 0.f));
     hi = fminf(fminf(fmaxf(a0, b0), fmaxf(a1, b1)), fminf(fmaxf(a2, b2), tmax));
-    h1 = lo <= hi;
+    h1 = lo <= hi * kSlabSlack;
     t1 = lo;
 }
 
@@ -434,7 +451,7 @@ MH_DEV void trav_inner_step4(TravLane &t, const Node4 *nodes, const LdsBvh &stk)
         const float a2 = __builtin_fmaf(lz[c], t.inv.z, -t.ood.z), b2 = __builtin_fmaf(hz[c], t.inv.z, -t.ood.z);
         const float lo = fmaxf(fmaxf(fminf(a0, b0), fminf(a1, b1)), fmaxf(fminf(a2, b2), 0.f));
         const float hi = fminf(fminf(fmaxf(a0, b0), fmaxf(a1, b1)), fminf(fmaxf(a2, b2), t.best));
-        const bool h = lo <= hi && rf[c] != 0xffffffffu;
+        const bool h = lo <= hi * kSlabSlack && rf[c] != 0xffffffffu;
         tc[c] = h ? lo : __builtin_huge_valf();
         rc[c] = rf[c];
         cnt += h ? 1u : 0u;
@@ -504,7 +521,7 @@ MH_DEV void trav_inner_step_q(TravLane &t, const QNode4 *nodes, const LdsBvh &st
         const float a2 = __builtin_fmaf(lz, t.inv.z, -t.ood.z), b2 = __builtin_fmaf(hz, t.inv.z, -t.ood.z);
         const float lo = fmaxf(fmaxf(fminf(a0, b0), fminf(a1, b1)), fmaxf(fminf(a2, b2), 0.f));
         const float hi = fminf(fminf(fmaxf(a0, b0), fmaxf(a1, b1)), fminf(fmaxf(a2, b2), t.best));
-        const bool h = lo <= hi && rf[c] != 0xffffffffu;
+        const bool h = lo <= hi * kSlabSlack && rf[c] != 0xffffffffu;
         tc[c] = h ? lo : __builtin_huge_valf();
         rc[c] = rf[c];
         cnt += h ? 1u : 0u;
