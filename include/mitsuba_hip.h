@@ -82,7 +82,9 @@ enum { MH_RFILTER_BOX = 0, MH_RFILTER_GAUSSIAN = 1 };         /* box.cpp, gaussi
 enum { MH_PIXEL_RGB = 0, MH_PIXEL_Y = 1, MH_PIXEL_XYZ = 2, MH_PIXEL_RGBA = 3, MH_PIXEL_YA = 4,
        MH_PIXEL_XYZA = 5 };
 enum { MH_MEDIUM_HETEROGENEOUS = 0, MH_MEDIUM_HOMOGENEOUS = 1 };
-enum { MH_PHASE_ISOTROPIC = 0, MH_PHASE_HG = 1 };
+/* isotropic.cpp, hg.cpp, rayleigh.cpp (depolarization 0 only: mh_medium::g must
+ * be 0 for it), tabphase.cpp (the table comes from mh_scene_set_phase_table) */
+enum { MH_PHASE_ISOTROPIC = 0, MH_PHASE_HG = 1, MH_PHASE_RAYLEIGH = 2, MH_PHASE_TABULATED = 3 };
 enum { MH_MEDIUM_NO_EMITTER_SAMPLING = 1u,        /* medium.cpp:29 sample_emitters = false */
        MH_MEDIUM_NO_SPECTRAL_EXTINCTION = 2u };   /* heterogeneous.cpp:161 has_spectral_extinction = false */
 enum { MH_INTEGRATOR_PATH = 0, MH_INTEGRATOR_VOLPATH = 1, MH_INTEGRATOR_PRB = 2,
@@ -199,7 +201,7 @@ typedef struct mh_emitter {
 typedef struct mh_medium {
     uint32_t type;              /* MH_MEDIUM_* */
     uint32_t phase;             /* MH_PHASE_* */
-    float g;                    /* HG asymmetry */
+    float g;                    /* HG: asymmetry; Rayleigh: depolarization (only 0 is accepted) */
     float scale;                /* sigma_t scale */
     float albedo[3];            /* constant single-scattering albedo */
     float sigma_t_const;        /* homogeneous: sigma_t (before scale) */
@@ -318,6 +320,24 @@ int mh_scene_update_texture(mh_scene *scene, uint32_t texture, const float *data
  * mh_scene_update_rgb: MH_ERR_INVALID_ARGUMENT for a NULL argument or an
  * emitter index out of bounds; ordered on the scene's stream. */
 int mh_scene_update_emitter(mh_scene *scene, uint32_t emitter, const float radiance[3]);
+/*
+ * The table of a MH_PHASE_TABULATED medium (TabulatedPhaseFunction,
+ * src/phase/tabphase.cpp; IrregularContinuousDistribution,
+ * include/mitsuba/core/distr_1d.h:618-991): `n` nodes `cost` (cos theta in the
+ * physics convention, +1 = forward scattering) with the unnormalised phase
+ * function `values` at them (host pointers).  Call it after mh_scene_create
+ * and before the first render; a second call replaces the table (traverse() /
+ * update() of '<medium>.phase_function.values'); no BVH or grid work happens.
+ * MH_ERR_INVALID_ARGUMENT unless 2 <= n <= 65536, every entry is finite, cost
+ * is strictly increasing and within [-1, 1], values >= 0, at least one interval
+ * has positive mass, and the medium's phase is MH_PHASE_TABULATED.  (The
+ * [-1, 1] bound is stricter than the reference, which does not check it: a
+ * node outside it can never be a cosine.)  Until a tabulated medium has its
+ * table, mh_render / mh_render_samples / mh_render_backward /
+ * mh_render_forward return MH_ERR_INVALID_ARGUMENT before any launch.
+ */
+int mh_scene_set_phase_table(mh_scene *scene, uint32_t medium, uint32_t n, const float *cost,
+                             const float *values);
 
 /*
  * Forward render into the un-developed film storage: RGBW (H*W*4 floats), or
@@ -417,6 +437,21 @@ int mh_trace_preliminary(mh_scene *scene, uint64_t n, const float *rays, float *
                          mh_stats *stats);
 int mh_trace_shadow(mh_scene *scene, uint64_t n, const float *rays, uint32_t *occluded,
                     uint32_t flags, mh_stats *stats);
+
+/*
+ * Phase-function queries of medium `medium`, in the spirit of mh_trace_*: the
+ * device functions the volumetric integrators call (PhaseFunction::sample /
+ * eval_pdf; isotropic, hg, rayleigh, tabphase), one lane per item.  Directions
+ * are in the local frame of the interaction, Frame3f(ray.d) with wi =
+ * (0, 0, -1), so the physics cos theta of wo is wo.z.  For every supported
+ * phase function value == pdf and the sampling weight is 1.
+ *   mh_phase_sample : u = SoA u1[n] u2[n] (sample2) -> wo = SoA x[n] y[n] z[n], pdf[n]
+ *   mh_phase_eval   : wo = SoA x[n] y[n] z[n] -> value[n]
+ * Host pointers, or device pointers with MH_FLAG_DEVICE_POINTERS.
+ */
+int mh_phase_sample(mh_scene *scene, uint32_t medium, uint64_t n, const float *u, float *wo, float *pdf,
+                    uint32_t flags);
+int mh_phase_eval(mh_scene *scene, uint32_t medium, uint64_t n, const float *wo, float *value, uint32_t flags);
 
 /* BVH introspection (host): #nodes, #primitives, max depth. */
 int mh_scene_bvh_info(mh_scene *scene, uint32_t *n_nodes, uint32_t *n_prims, uint32_t *depth);

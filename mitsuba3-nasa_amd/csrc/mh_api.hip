@@ -120,6 +120,8 @@ struct mh_scene {
     // device buffers
     DevBuf nodes, nodes4, primsc, stack_ovf, prims, prim_pairs, key_sp, shapes, bsdf_type, bsdf_tex, textures, emitters, positions, normals,
         texcoords, faces, texels, media, grid;
+    DevBuf phase_tab;  // the tabulated phase functions' tables, one after the other (DScene::phase_tab)
+    std::vector<std::vector<PhaseRec>> h_phase_tabs;  // per medium (empty: none set)
     DevBuf work, film_tmp, film4, alpha_px, counters, grad_meta, tmp_a, tmp_b, tmp_c, tmp_d, tmp_e, weights_tmp;
     std::vector<uint8_t> meta_host;  // the bytes last uploaded to grad_meta (upload_slots)
     DevBuf wf_ws, wf_ctr;  // wavefront state (SoA) and per-chunk/bounce queue counters
@@ -355,6 +357,15 @@ int mh_scene_create(const mh_scene_desc *desc, int device, void *stream, mh_scen
             return fail(MH_ERR_UNSUPPORTED, "mh_scene_create: volume grid above 2^32 texels");
         if (a.phase == MH_PHASE_HG && !(a.g > -1.f && a.g < 1.f))
             return fail(MH_ERR_INVALID_ARGUMENT, "The asymmetry parameter must lie in the interval (-1, 1)!");
+        if (a.phase > MH_PHASE_TABULATED)
+            return fail(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: unknown phase function");
+        // rayleigh.cpp:124-126 returns a value that differs from the pdf when
+        // depolarization != 0 (the sampling weight is then not 1)
+        if (a.phase == MH_PHASE_RAYLEIGH && a.g != 0.f)
+            return fail(MH_ERR_INVALID_ARGUMENT,
+                        "mh_scene_create: the rayleigh phase function is supported with depolarization = 0 only: "
+                        "otherwise its value differs from its sampling density and the sampling weight is not 1, "
+                        "which the volumetric integrators here do not carry");
     }
     if (desc->sensor.pixel_format > MH_PIXEL_XYZA)
         return fail(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: unknown pixel format");
@@ -370,6 +381,7 @@ int mh_scene_create(const mh_scene_desc *desc, int device, void *stream, mh_scen
     }
     s->h_media.assign(desc->media, desc->media + desc->n_media);
     s->h_dmedia = meds;
+    s->h_phase_tabs.assign(desc->n_media, {});
     s->n_media = desc->n_media;
     if (desc->sensor.medium != MH_INVALID && desc->sensor.medium >= desc->n_media)
         return fail(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: sensor medium index out of bounds");
@@ -440,6 +452,8 @@ int mh_scene_create(const mh_scene_desc *desc, int device, void *stream, mh_scen
     S.texels = s->texels.as<float>();
     S.media = s->media.as<DMedium>();
     S.grid = s->grid.as<float>();
+    S.phase_tab = nullptr;  // mh_scene_set_phase_table
+    S.phase_tab_bytes = S.phase_lds_bytes = 0;
     S.n_media = desc->n_media;
     S.camera_medium = desc->sensor.medium;
     S.vol_flags = 0;
@@ -447,6 +461,9 @@ int mh_scene_create(const mh_scene_desc *desc, int device, void *stream, mh_scen
         for (uint32_t mm : {desc->shapes[i].interior_medium, desc->shapes[i].exterior_medium})
             if (mm != MH_INVALID)
                 S.vol_flags |= desc->media[mm].type == MH_MEDIUM_HOMOGENEOUS ? kVolNeeHomogeneous : kVolHandleNull;
+    for (uint32_t i = 0; i < desc->n_media; ++i)
+        if (desc->media[i].phase == MH_PHASE_RAYLEIGH || desc->media[i].phase == MH_PHASE_TABULATED)
+            S.vol_flags |= kVolPhaseExt;
     S.n_shapes = desc->n_shapes;
     S.n_bsdfs = desc->n_bsdfs;
     S.n_textures = desc->n_textures;
@@ -556,7 +573,7 @@ int mh_scene_destroy(mh_scene *s) {
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     for (DevBuf *b : {&s->nodes, &s->nodes4, &s->primsc, &s->stack_ovf, &s->prims, &s->prim_pairs, &s->key_sp, &s->shapes, &s->bsdf_type, &s->bsdf_tex, &s->textures,
                       &s->emitters, &s->positions, &s->normals, &s->texcoords, &s->faces, &s->texels,
-                      &s->media, &s->grid, &s->work, &s->film_tmp, &s->film4, &s->alpha_px, &s->counters, &s->grad_meta, &s->tmp_a, &s->tmp_b,
+                      &s->media, &s->grid, &s->phase_tab, &s->work, &s->film_tmp, &s->film4, &s->alpha_px, &s->counters, &s->grad_meta, &s->tmp_a, &s->tmp_b,
                       &s->tmp_c, &s->tmp_d, &s->tmp_e, &s->weights_tmp, &s->wf_ws, &s->wf_ctr, &s->wf_ws_prb, &s->wf_partial, &s->gw, &s->wf_carry, &s->wf_ws_bmp, &s->wf_ws_det, &s->pvp_log, &s->pvp_main, &s->pvp_ovf, &s->grid_corner, &s->fx_word, &s->bmp_fx,
                       &s->shard_w, &s->shard_tmp, &s->shard_g, &s->replay_fx, &s->wf_ws2, &s->wf_ws_prb2,
                       &s->wf_ws_bmp2, &s->wf_partial2, &s->work2, &s->wf_carry2, &s->stack_ovf2})
@@ -678,6 +695,131 @@ int mh_scene_update_medium(mh_scene *s, uint32_t medium, const float *albedo, co
     MH_HIP(hipMemcpyAsync(s->media.as<DMedium>() + medium, &b, sizeof(DMedium), hipMemcpyHostToDevice, s->stream));
     MH_HIP(hipStreamSynchronize(s->stream));
     return MH_OK;
+}
+
+// The table of a tabulated phase function: what IrregularContinuousDistribution
+// ::compute_cdf_scalar builds (distr_1d.h:916-978) -- the interval integrals
+// accumulated in double and stored as float, the first and last interval with
+// positive mass, integral = cdf[valid.y], normalization = 1 / integral -- in
+// the PhaseRec layout (mh_device.hpp).  All tables share one device buffer;
+// the media records carry offset, size and the valid intervals.
+int mh_scene_set_phase_table(mh_scene *s, uint32_t medium, uint32_t n, const float *cost, const float *values) {
+    const char *fn = "mh_scene_set_phase_table: ";
+    auto bad = [&](const char *why) { return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + why); };
+    if (!s || !cost || !values) return bad("NULL argument");
+    if (medium >= s->n_media) return bad("medium index out of bounds");
+    if (s->h_dmedia[medium].phase != MH_PHASE_TABULATED) return bad("the medium's phase function is not MH_PHASE_TABULATED");
+    if (n < 2) return bad("IrregularContinuousDistribution: needs at least two entries!");
+    if (n > 65536) return bad("more than 65536 entries");
+    std::vector<PhaseRec> tab((size_t)n + 2);
+    uint32_t first = MH_INVALID, last = MH_INVALID;
+    double integral = 0.;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!std::isfinite(cost[i]) || !std::isfinite(values[i])) return bad("entries must be finite");
+        if (cost[i] < -1.f || cost[i] > 1.f) return bad("'cost' must lie in [-1, 1]");
+        if (values[i] < 0.f) return bad("IrregularContinuousDistribution: entries must be non-negative!");
+        PhaseRec &r = tab[1 + i];
+        r.x = cost[i];
+        r.y = values[i];
+        r.c_prev = (float)integral;   // cdf[i - 1]; 0 for i == 0
+        if (i + 1 < n) {
+            if (!(cost[i + 1] > cost[i]))
+                return bad("IrregularContinuousDistribution: node positions must be strictly increasing!");
+            const double value = 0.5 * ((double)cost[i + 1] - (double)cost[i]) * ((double)values[i] + (double)values[i + 1]);
+            integral += value;
+            if (value > 0.) {
+                if (first == MH_INVALID) first = i;
+                last = i;
+            }
+        }
+        r.c = (float)integral;        // cdf[i]; the last node repeats cdf[n - 2]
+    }
+    if (first == MH_INVALID) return bad("IrregularContinuousDistribution: no probability mass found!");
+    const float total = tab[1 + last].c;   // m_integral = cdf[valid.y]
+    if (!(total > 0.f) || !std::isfinite(1.f / total)) return bad("the table's integral is not a normal float");
+    tab[0] = PhaseRec{total, 1.f / total, cost[0], cost[n - 1]};
+    tab[1 + n] = PhaseRec{std::numeric_limits<float>::infinity(), 0.f, total, total};
+    MH_HIP(hipSetDevice(s->device));
+    MH_HIP(hipStreamSynchronize(s->stream));  // earlier calls may still read the old tables
+    // the new media records and the concatenated tables are built aside and
+    // become the scene's only after the last HIP call has succeeded
+    std::vector<DMedium> media = s->h_dmedia;
+    std::vector<PhaseRec> all;
+    for (uint32_t m = 0; m < s->n_media; ++m) {
+        const std::vector<PhaseRec> &t = m == medium ? tab : s->h_phase_tabs[m];
+        if (t.empty()) continue;
+        DMedium &b = media[m];
+        b.tab_offset = (uint32_t)all.size();
+        b.tab_n = (uint32_t)t.size() - 2u;
+        if (m == medium) b.tab_valid = first | (last << 16);
+        all.insert(all.end(), t.begin(), t.end());
+    }
+    // a buffer of its own: a failure leaves the old tables and the records that point into them in place
+    DevBuf buf;
+    hipError_t e = upload(buf, all.data(), all.size(), s->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(s->media.ptr, media.data(), sizeof(DMedium) * s->n_media, hipMemcpyHostToDevice, s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    if (e != hipSuccess) {
+        buf.release();
+        return set_error(MH_ERR_HIP, std::string(fn) + hipGetErrorString(e));
+    }
+    s->phase_tab.release();
+    s->phase_tab = buf;
+    s->h_phase_tabs[medium] = std::move(tab);
+    s->h_dmedia = std::move(media);
+    s->S.phase_tab = s->phase_tab.as<PhaseRec>();
+    s->S.phase_tab_bytes = (uint32_t)(all.size() * sizeof(PhaseRec));
+    return MH_OK;
+}
+
+// a tabulated medium without its table: the kernels would read a null table
+static int check_phase_tables(const mh_scene *s, const char *fn) {
+    for (uint32_t m = 0; m < s->n_media; ++m)
+        if (s->h_dmedia[m].phase == MH_PHASE_TABULATED && s->h_dmedia[m].tab_n == 0)
+            return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + ": medium " + std::to_string(m) +
+                                                          " has a tabulated phase function but no table "
+                                                          "(call mh_scene_set_phase_table after mh_scene_create)");
+    return MH_OK;
+}
+
+// Phase-function queries: a grid-stride kernel around phase_sample / phase_eval
+static int phase_query(mh_scene *s, const char *fn, bool sample, uint32_t medium, uint64_t n, const float *in,
+                       float *out, float *pdf, uint32_t flags) {
+    if (!s) return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + ": NULL scene");
+    if (medium >= s->n_media) return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + ": medium index out of bounds");
+    if (n && (!in || !out || (sample && !pdf))) return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + ": NULL argument");
+    if (n >= (1ull << 32)) return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + ": more than 2^32 - 1 items");
+    if (int rc = check_phase_tables(s, fn)) return rc;
+    if (n == 0) return MH_OK;
+    MH_HIP(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
+    const bool dev = flags & MH_FLAG_DEVICE_POINTERS;
+    const uint64_t n_in = sample ? 2 * n : 3 * n, n_out = sample ? 3 * n : n;
+    const float *d_in = in;
+    float *d_out = out, *d_pdf = pdf;
+    if (!dev) {
+        MH_HIP(s->tmp_a.alloc(n_in * 4));
+        MH_HIP(hipMemcpyAsync(s->tmp_a.ptr, in, n_in * 4, hipMemcpyHostToDevice, st));
+        d_in = s->tmp_a.as<float>();
+        MH_HIP(s->tmp_b.alloc((n_out + n) * 4));
+        d_out = s->tmp_b.as<float>();
+        d_pdf = d_out + n_out;
+    }
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)device_cus(s->device) * 8);
+    MH_HIP(launch_phase_query(s->S, sample, medium, n, d_in, d_out, d_pdf, grid, st));
+    if (!dev) {
+        MH_HIP(hipMemcpyAsync(out, d_out, n_out * 4, hipMemcpyDeviceToHost, st));
+        if (sample) MH_HIP(hipMemcpyAsync(pdf, d_pdf, n * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (!(flags & MH_FLAG_NO_SYNC) || !dev) MH_HIP(hipStreamSynchronize(st));
+    return MH_OK;
+}
+int mh_phase_sample(mh_scene *s, uint32_t medium, uint64_t n, const float *u, float *wo, float *pdf, uint32_t flags) {
+    return phase_query(s, "mh_phase_sample", true, medium, n, u, wo, pdf, flags);
+}
+int mh_phase_eval(mh_scene *s, uint32_t medium, uint64_t n, const float *wo, float *value, uint32_t flags) {
+    return phase_query(s, "mh_phase_eval", false, medium, n, wo, value, nullptr, flags);
 }
 
 // ---------------------------------------------------------------------------
@@ -936,6 +1078,7 @@ static int render_impl(mh_scene *s, const mh_integrator *in, uint32_t seed, uint
         return set_error(MH_ERR_INVALID_ARGUMENT, "\"rr_depth\" must be set to a value greater than zero!");
     if (spp == 0) return set_error(MH_ERR_INVALID_ARGUMENT, "mh_render: spp must be > 0");
     if (int rc = check_reduce_flags(s, flags, "mh_render", true)) return rc;
+    if (int rc = check_phase_tables(s, "mh_render")) return rc;
     double t_start = now_ms();
     if (stats) *stats = mh_stats{};
     Layout L;
@@ -1158,6 +1301,7 @@ int mh_render_samples(mh_scene *s, const mh_integrator *in, uint32_t seed, uint3
     if (in->type > MH_INTEGRATOR_PRBVOLPATH)
         return set_error(MH_ERR_UNSUPPORTED, "mh_render_samples: unsupported integrator");
     if (spp == 0 || in->rr_depth == 0) return set_error(MH_ERR_INVALID_ARGUMENT, "mh_render_samples: bad arguments");
+    if (int rc = check_phase_tables(s, "mh_render_samples")) return rc;
     Layout L;
     const bool ad = in->type == MH_INTEGRATOR_PRB || in->type == MH_INTEGRATOR_PRBVOLPATH;
     int rc = make_layout(s, spp, spp_begin, spp_end, L, ad);
@@ -1446,6 +1590,7 @@ static int render_backward_impl(mh_scene *s, const mh_integrator *in, uint32_t s
         return set_error(MH_ERR_INVALID_ARGUMENT, "\"rr_depth\" must be set to a value greater than zero!");
     if (spp == 0) return set_error(MH_ERR_INVALID_ARGUMENT, "mh_render_backward: spp must be > 0");
     if (int rc = check_reduce_flags(s, flags, "mh_render_backward", false)) return rc;
+    if (int rc = check_phase_tables(s, "mh_render_backward")) return rc;
     double t_start = now_ms();
     if (stats) *stats = mh_stats{};
     Layout L;
@@ -1897,6 +2042,7 @@ static int render_forward_impl(mh_scene *s, const mh_integrator *in, uint32_t se
         return set_error(MH_ERR_INVALID_ARGUMENT, "\"rr_depth\" must be set to a value greater than zero!");
     if (spp == 0) return set_error(MH_ERR_INVALID_ARGUMENT, "mh_render_forward: spp must be > 0");
     if (int rc = check_reduce_flags(s, flags, "mh_render_forward", true)) return rc;
+    if (int rc = check_phase_tables(s, "mh_render_forward")) return rc;
     const double t_start = now_ms();
     if (stats) *stats = mh_stats{};
     Layout L;

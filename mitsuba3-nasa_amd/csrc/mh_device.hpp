@@ -137,12 +137,25 @@ struct DEmitter {
     float center[3], radius;   // constant / directional: scene bounding sphere
 };
 
+// One record of a tabulated phase function's table (DScene::phase_tab; built
+// by mh_scene_set_phase_table from IrregularContinuousDistribution's nodes,
+// pdf and cdf, distr_1d.h:916-978).  A medium's table is a header
+// {integral, normalization, range.x, range.y} at tab_offset, then one record
+// per node i at tab_offset + 1 + i: {nodes[i], pdf[i], cdf[i - 1] (0 for
+// i == 0), cdf[i] (cdf[n - 2] for the last node)}, then one more record with
+// x = +inf that a search for a value beyond the range may read.  Interval i
+// is records i and i + 1: one 32-byte fetch after the search.
+struct alignas(16) PhaseRec { float x, y, c_prev, c; };
+
 struct DMedium {
-    uint32_t type, phase, flags, pad0;
+    uint32_t type, phase, flags;
+    uint32_t tab_offset;                  // tabulated phase: first record (the header) in DScene::phase_tab
     float g, scale, maj, sigma_t_const;   // maj = scale * max(grid) (heterogeneous.cpp:163)
     float albedo[4];
     uint32_t res[4];
-    uint64_t grid_offset, pad1;   // grid_offset: first float of the medium's bricked grid (grid_index)
+    uint64_t grid_offset;   // first float of the medium's bricked grid (grid_index)
+    uint32_t tab_n;         // tabulated phase: nodes (0: no table yet)
+    uint32_t tab_valid;     // its first | last << 16 interval with positive mass (m_valid)
     float to_local[12];
     float bbox_min[4], bbox_max[4];
 };
@@ -150,6 +163,9 @@ struct DMedium {
 // PRBVolpathIntegrator.prepare_scene (prbvolpath.py:76-89), from the media of the shapes
 constexpr uint32_t kVolHandleNull = 1u;       // some medium is heterogeneous
 constexpr uint32_t kVolNeeHomogeneous = 2u;   // some medium is homogeneous
+// not prepare_scene's: some medium's phase function is rayleigh or tabulated
+// (launch_vol_sched: volpath's machine with those branches; else the one without)
+constexpr uint32_t kVolPhaseExt = 4u;
 
 struct DScene {                 // kernel argument (by value)
     const Node *nodes;
@@ -199,6 +215,9 @@ struct DScene {                 // kernel argument (by value)
     // as the device's division), so the bounce kernels hold no per-lane loop-invariant quotients
     float inv_width, inv_height, inv_n_emitters;
     float n_emitters_f, env_pdf;  // (float)n_emitters; kInv4Pi * inv_n_emitters (a constant emitter's pdf)
+    const PhaseRec *phase_tab;    // the tabulated phase functions' tables (DMedium::tab_offset; nullptr: none)
+    uint32_t phase_tab_bytes;     // their size
+    uint32_t phase_lds_bytes;     // per launch: phase_tab_bytes when k_vol_sched stages them into LDS, else 0
 };
 
 // lane -> (pixel, sample) map of one render call (sample-slab aware)

@@ -939,6 +939,35 @@ hipError_t launch_trace(const DScene &S, bool shadow, uint64_t n, const float *r
     return hipGetLastError();
 }
 
+// mh_phase_sample / mh_phase_eval: phase_sample / phase_eval of one medium, as
+// the volumetric integrators call them, one item per lane (SoA in and out)
+__global__ void __launch_bounds__(256)
+k_phase_sample(DScene S, uint32_t medium, uint64_t n, const float *__restrict__ u, float *__restrict__ wo,
+               float *__restrict__ pdf) {
+    const DMedium &m = S.media[medium];
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        float p;
+        const V3 w = phase_sample(S, m, u[i], u[n + i], p);
+        wo[i] = w.x; wo[n + i] = w.y; wo[2 * n + i] = w.z;
+        pdf[i] = p;
+    }
+}
+__global__ void __launch_bounds__(256)
+k_phase_eval(DScene S, uint32_t medium, uint64_t n, const float *__restrict__ wo, float *__restrict__ value) {
+    const DMedium &m = S.media[medium];
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        value[i] = phase_eval(S, m, v3(wo[i], wo[n + i], wo[2 * n + i]));
+}
+hipError_t launch_phase_query(const DScene &S, bool sample, uint32_t medium, uint64_t n, const float *in,
+                              float *wo_or_value, float *pdf, uint32_t grid, hipStream_t st) {
+    if (n == 0 || grid == 0) return hipSuccess;
+    if (sample) hipLaunchKernelGGL(k_phase_sample, dim3(grid), dim3(256), 0, st, S, medium, n, in, wo_or_value, pdf);
+    else hipLaunchKernelGGL(k_phase_eval, dim3(grid), dim3(256), 0, st, S, medium, n, in, wo_or_value);
+    return hipGetLastError();
+}
+
 hipError_t launch_render(const DScene &S, const IntegratorParams &in, const LaneMap &lm,
                          uint32_t seed_value, uint32_t n_passes, uint64_t n, uint64_t plane,
                          float *out, unsigned long long *counters, hipStream_t st, int alpha) {

@@ -63,6 +63,18 @@ inline Split split_chunks(uint64_t n_px, uint64_t per_pixel, uint64_t max_sample
     return c;
 }
 
+// k_vol_sched keeps the tables of the tabulated phase functions in LDS (a
+// sample or an evaluation is a dependent chain of about log2(nodes) loads) when
+// they fit beside what the launch already holds there -- BVH, traversal
+// stacks, shading tables, media records, deferral scratch, the machine's
+// static arrays -- within the 64 KiB of a workgroup; else they stay in global
+// memory.  The results are the same either way.
+constexpr uint64_t kLdsPerWorkgroup = 65536;
+inline uint32_t phase_lds_bytes(uint32_t table_bytes, uint64_t other_lds_bytes) {
+    return table_bytes && other_lds_bytes <= kLdsPerWorkgroup && table_bytes <= kLdsPerWorkgroup - other_lds_bytes
+               ? table_bytes : 0u;
+}
+
 // What a call knows about itself and its scene.
 struct Facts {
     uint32_t type = 0, max_depth = 0, flags = 0;  // the integrator, the call's flags

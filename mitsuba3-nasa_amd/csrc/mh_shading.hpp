@@ -2753,11 +2753,69 @@ MH_DEV float eval_hg(float g, float cos_theta) {
     float temp = (1.f + g * g) + (2.f * g) * cos_theta;
     return (kInv4Pi * (1.f - g * g)) / (temp * __builtin_sqrtf(temp));
 }
-MH_DEV float phase_eval(const DMedium &m, V3 wo) {
+// TabulatedPhaseFunction (phase/tabphase.cpp:91-135) over the fork's
+// IrregularContinuousDistribution (core/distr_1d.h), on the PhaseRec table T
+// of the medium (mh_device.hpp): T[0] = {integral, normalization, range.x,
+// range.y}, T[1 + i] = node i.  Both searches are dr::binary_search
+// (drjit/array_router.h) with its fixed trip count, log2i(end - start) + 1,
+// and no branch in the trip, so the lanes of a wave stay converged.
+constexpr float kInvTwoPi = 0.15915494309189533577f;
+// eval_pdf_normalized (distr_1d.h:707-736): 0 outside [nodes[0], nodes[n - 1]]
+MH_DEV float tab_eval_pdf(const PhaseRec *__restrict__ T, uint32_t n, float x) {
+    const PhaseRec h = T[0];
+    const PhaseRec *__restrict__ R = T + 1;
+    const bool active = x >= h.c_prev && x <= h.c;
+    uint32_t start = 0u, end = n;
+    for (uint32_t it = 32u - (uint32_t)__builtin_clz(n); it; --it) {
+        const uint32_t mid = (start + end) >> 1;   // <= n: the table ends in a record past the last node
+        const bool c = R[mid].x < x;
+        start = c ? min(mid + 1u, end) : start;
+        end = c ? end : mid;
+    }
+    const uint32_t i = max(min(start, n - 1u), 1u) - 1u;
+    const PhaseRec a = R[i], b = R[i + 1u];
+    const float t = (x - a.x) / (b.x - a.x);
+    return (active ? __builtin_fmaf(t, b.y - a.y, a.y) : 0.f) * h.y;
+}
+// sample (distr_1d.h:781-814), the search with the JIT variants' predicate
+// over [valid.x, valid.y]: it never ends in an interval without mass
+MH_DEV float tab_sample(const PhaseRec *__restrict__ T, uint32_t valid, float u) {
+    const float integral = T[0].x;
+    const PhaseRec *__restrict__ R = T + 1;
+    const float s = u * integral;
+    uint32_t start = valid & 0xffffu, end = valid >> 16;
+    for (uint32_t it = end > start ? 32u - (uint32_t)__builtin_clz(end - start) : 0u; it; --it) {
+        const uint32_t mid = (start + end) >> 1;
+        const float v = R[mid].c;
+        const bool c = (v < s || v == 0.f) && v != integral;
+        start = c ? min(mid + 1u, end) : start;
+        end = c ? end : mid;
+    }
+    const PhaseRec a = R[start], b = R[start + 1u];
+    const float w = b.x - a.x, q = (s - a.c_prev) / w;
+    const float t_linear = (a.y - __builtin_sqrtf(fmaxf(a.y * a.y + (2.f * q) * (b.y - a.y), 0.f))) / (a.y - b.y),
+                t_const = q / a.y;
+    return __builtin_fmaf(a.y == b.y ? t_const : t_linear, w, a.x);
+}
+// RayleighPhaseFunction without depolarization (phase/rayleigh.cpp:50-52)
+MH_DEV float eval_rayleigh(float cos_theta) { return ((3.f / 16.f) * kInvPi) * (1.f + cos_theta * cos_theta); }
+
+// wo is local to Frame3f(ray.d) with wi = (0, 0, -1): the fork's tabphase and
+// rayleigh take the physics cosine (+1 = forward), which is wo.z there.
+// Ext = false leaves the two out: config 4 (HG) measured 1.2 % slower on
+// k_vol_sched<VolMachine> with them in its instruction stream
+// (profiles/phase_bench.txt), so a scene without such a medium runs that
+// machine without them (kVolPhaseExt).
+template <bool Ext = true>
+MH_DEV float phase_eval(const DScene &S, const DMedium &m, V3 wo) {
     if (m.phase == MH_PHASE_HG) return eval_hg(m.g, dot(wo, v3(0.f, 0.f, -1.f)));
+    if (!Ext) return kInv4Pi;
+    if (m.phase == MH_PHASE_TABULATED) return tab_eval_pdf(S.phase_tab + m.tab_offset, m.tab_n, wo.z) * kInvTwoPi;
+    if (m.phase == MH_PHASE_RAYLEIGH) return eval_rayleigh(wo.z);
     return kInv4Pi;
 }
-MH_DEV V3 phase_sample(const DMedium &m, float s2x, float s2y, float &pdf) {
+template <bool Ext = true>
+MH_DEV V3 phase_sample(const DScene &S, const DMedium &m, float s2x, float s2y, float &pdf) {
     if (m.phase == MH_PHASE_HG) {
         const float g = m.g;
         float sqr_term = (1.f - g * g) / ((1.f - g) + (2.f * g) * s2x);
@@ -2768,6 +2826,21 @@ MH_DEV V3 phase_sample(const DMedium &m, float s2x, float s2y, float &pdf) {
         sincos_cephes((2.f * kPi) * s2y, sp, cp);
         pdf = eval_hg(g, -cos_theta);
         return v3(sin_theta * cp, sin_theta * sp, cos_theta);
+    }
+    if (Ext && (m.phase == MH_PHASE_TABULATED || m.phase == MH_PHASE_RAYLEIGH)) {
+        float cos_theta;
+        if (m.phase == MH_PHASE_TABULATED) {   // tabphase.cpp:99-119 (wo is not negated: the "[Kate]" note)
+            cos_theta = tab_sample(S.phase_tab + m.tab_offset, m.tab_valid, s2x);
+        } else {                               // rayleigh.cpp:104-113
+            const float z = 2.f * (2.f * s2x - 1.f), tmp = __builtin_sqrtf(z * z + 1.f);
+            cos_theta = cbrtf(z + tmp) + cbrtf(z - tmp);
+        }
+        const float sin_theta = __builtin_sqrtf(fmaxf(1.f - cos_theta * cos_theta, 0.f));
+        float sp, cp;
+        sincos_cephes((2.f * kPi) * s2y, sp, cp);
+        const V3 wo = v3(sin_theta * cp, sin_theta * sp, cos_theta);
+        pdf = phase_eval(S, m, wo);
+        return wo;
     }
     pdf = kInv4Pi;
     return square_to_uniform_sphere(s2x, s2y);
@@ -3004,7 +3077,7 @@ MH_DEV bool volpath_pre(const DScene &S, const LdsBvh &B, const IntegratorParams
         v.valid = true;  // valid_ray |= act_medium_scatter (volpath.cpp:223)
         if (sample_emitters) {
             walk = nee_begin(S, mei.p, v3(0, 0, 0), nullptr, rng, medium, v.ds, v.ns);
-            const float ph = phase_eval(m, mei_to_local(mei, v.ds.d));
+            const float ph = phase_eval(S, m, mei_to_local(mei, v.ds.d));
             v.pend = throughput * ph;
             v.pend_w = mis_weight(v.ds.pdf, v.ds.delta ? 0.f : ph);
             v.nee_kind = kNeeMedium;
@@ -3055,6 +3128,7 @@ MH_DEV bool volpath_pre(const DScene &S, const LdsBvh &B, const IntegratorParams
 
 // post: the emitter sample's contribution, then phase / BSDF sampling; false
 // when the path has ended
+template <bool Ext = true>
 MH_DEV bool volpath_post(const DScene &S, const IntegratorParams &in, Pcg &rng, VolState &v) {
     V3 &throughput = v.throughput, &result = v.result;
     if (v.nee_kind == kNeeMedium) result = result + (v.pend * nee_result(v.ns)) * v.pend_w;
@@ -3066,7 +3140,7 @@ MH_DEV bool volpath_post(const DScene &S, const IntegratorParams &in, Pcg &rng, 
         (void)rng.next_float();
         const float s2x = rng.next_float(), s2y = rng.next_float();
         float ph_pdf;
-        V3 wo = phase_sample(m, s2x, s2y, ph_pdf);
+        V3 wo = phase_sample<Ext>(S, m, s2x, s2y, ph_pdf);
         act_scatter = act_scatter && ph_pdf > 0.f;
         if (act_scatter) {
             v.ray = spawn_ray(mei.p, v3(0, 0, 0), mei_to_world(mei, wo));
@@ -3622,7 +3696,7 @@ MH_DEV V3 prbvol_sample(const DScene &S, const LdsBvh &B, const IntegratorParams
                 nee_w = bv;
                 nee_pdf = bp;
             } else {
-                const float ph = phase_eval(S.media[med], mei_to_local(mei, ds.d));
+                const float ph = phase_eval(S, S.media[med], mei_to_local(mei, ds.d));
                 nee_w = v3(ph, ph, ph);
                 nee_pdf = ph;
             }
@@ -3661,7 +3735,7 @@ MH_DEV V3 prbvol_sample(const DScene &S, const LdsBvh &B, const IntegratorParams
             (void)rng.next_float();
             const float s2x = rng.next_float(), s2y = rng.next_float();
             float ph_pdf;
-            const V3 wo = phase_sample(S.media[med], s2x, s2y, ph_pdf);
+            const V3 wo = phase_sample(S, S.media[med], s2x, s2y, ph_pdf);
             act_scatter = act_scatter && ph_pdf > 0.f;
             if (act_scatter) {
                 ray = spawn_ray(mei.p, v3(0.f, 0.f, 0.f), mei_to_world(mei, wo));

@@ -47,6 +47,7 @@
 
 #include "mh_env.hpp"
 #include "mh_internal.hpp"
+#include "mh_plan.hpp"
 #include "mh_shading.hpp"
 
 namespace mh {
@@ -469,12 +470,13 @@ struct WMei {
 };
 
 // end of a trip that needs no walk (volpath_pre's tail + volpath_post)
+template <bool Ext>
 MH_DEV uint32_t vs_no_walk(const DScene &S, const IntegratorParams &in, Pcg &rng, VolState &v) {
     if (v.nee_kind != kNeeNone) {  // ds.pdf == 0: emitted = 0
         v.ns.transmittance = v3(0, 0, 0);
         v.ns.emitter_val = v3(0, 0, 0);
     }
-    return volpath_post(S, in, rng, v) ? kPhHead : kPhFree;
+    return volpath_post<Ext>(S, in, rng, v) ? kPhHead : kPhFree;
 }
 
 // the medium block of volpath_pre after its (optional) intersection, up to
@@ -551,6 +553,7 @@ MH_DEV uint32_t vs_head(const DScene &S, const IntegratorParams &in, Pcg &rng, V
 }
 
 // SCATTER: a real medium interaction (volpath.cpp:224-252)
+template <bool Ext>
 MH_DEV uint32_t vs_scatter(const DScene &S, const IntegratorParams &in, Pcg &rng, VolState &v) {
     mei_frame(v.mei);  // the merged medium step samples without it (identical values)
     const DMedium &m = S.media[v.medium];
@@ -564,17 +567,18 @@ MH_DEV uint32_t vs_scatter(const DScene &S, const IntegratorParams &in, Pcg &rng
     bool walk = false;
     if (sample_emitters) {
         walk = nee_begin(S, mei.p, v3(0, 0, 0), nullptr, rng, v.medium, v.ds, v.ns);
-        const float ph = phase_eval(m, mei_to_local(mei, v.ds.d));
+        const float ph = phase_eval<Ext>(S, m, mei_to_local(mei, v.ds.d));
         v.pend = v.throughput * ph;
         v.pend_w = mis_weight(v.ds.pdf, v.ds.delta ? 0.f : ph);
         v.nee_kind = kNeeMedium;
     }
     v.active_surface = false;
     v.rho = v3(0, 0, 0);
-    return walk ? kPhWalk : vs_no_walk(S, in, rng, v);
+    return walk ? kPhWalk : vs_no_walk<Ext>(S, in, rng, v);
 }
 
 // SURF: a surface interaction after its intersection (volpath.cpp:254-300)
+template <bool Ext>
 MH_DEV uint32_t vs_surf(const DScene &S, const IntegratorParams &in, Pcg &rng, VolState &v) {
     const SI &si = v.si;
     const bool count_direct = v.depth == 0 || v.specular_chain;
@@ -603,7 +607,7 @@ MH_DEV uint32_t vs_surf(const DScene &S, const IntegratorParams &in, Pcg &rng, V
             v.nee_kind = kNeeSurface;
         }
     }
-    return walk ? kPhWalk : vs_no_walk(S, in, rng, v);
+    return walk ? kPhWalk : vs_no_walk<Ext>(S, in, rng, v);
 }
 
 // ---- the walk (nee_step, volpath.cpp:361-448) cut at its intersection ------
@@ -1091,7 +1095,7 @@ MH_DEV uint32_t pv_post(const DScene &S, const LdsBvh &B, const IntegratorParams
             nee_w = bv;
             nee_pdf = bp;
         } else {
-            const float ph = phase_eval(S.media[v.med], mei_to_local(v.mei, v.ds.d));
+            const float ph = phase_eval(S, S.media[v.med], mei_to_local(v.mei, v.ds.d));
             nee_w = v3(ph, ph, ph);
             nee_pdf = ph;
         }
@@ -1108,7 +1112,7 @@ MH_DEV uint32_t pv_post(const DScene &S, const LdsBvh &B, const IntegratorParams
         (void)rng.next_float();
         const float s2x = rng.next_float(), s2y = rng.next_float();
         float ph_pdf;
-        const V3 wo = phase_sample(S.media[v.med], s2x, s2y, ph_pdf);
+        const V3 wo = phase_sample(S, S.media[v.med], s2x, s2y, ph_pdf);
         act_scatter = act_scatter && ph_pdf > 0.f;
         if (act_scatter) {
             v.ray = spawn_ray(v.mei.p, v3(0.f, 0.f, 0.f), mei_to_world(v.mei, wo));
@@ -1210,11 +1214,14 @@ MH_DEV uint32_t pv_trace(const DScene &S, const LdsBvh &B, const IntegratorParam
 #ifndef MH_PVB_MERGE
 #define MH_PVB_MERGE 0
 #endif
-struct VolMachine {
+// Ext: with the rayleigh and tabulated phase functions' branches (phase_eval)
+template <bool Ext>
+struct VolMachineT {
     using State = VolState;
     // kMergeMed: HEAD and WALK lanes share a trip (vs_medium_step)
     static constexpr bool kPrb = false, kWritesPos = true, kDeferEnd = false, kMergeMed = MH_VS_MERGE != 0;
-    MH_DEV VolMachine(const VsBwdArgs &, const LaneMap &, uint32_t) {}
+    static constexpr bool kPhaseTab = Ext;  // k_vol_sched stages the phase tables (DScene::phase_lds_bytes)
+    MH_DEV VolMachineT(const VsBwdArgs &, const LaneMap &, uint32_t) {}
     MH_DEV void init(const DScene &S, const IntegratorParams &in, Pcg &rng, RayT r, State &v, float, float) {
         volpath_init(S, in, rng, r, v);
     }
@@ -1227,10 +1234,10 @@ struct VolMachine {
         return vs_trace<Pk>(S, B, in, rng, ph, v, wm, nc, ns);
     }
     MH_DEV uint32_t scatter(const DScene &S, const IntegratorParams &in, Pcg &rng, State &v) {
-        return vs_scatter(S, in, rng, v);
+        return vs_scatter<Ext>(S, in, rng, v);
     }
     MH_DEV uint32_t surf(const DScene &S, const IntegratorParams &in, Pcg &rng, State &v) {
-        return vs_surf(S, in, rng, v);
+        return vs_surf<Ext>(S, in, rng, v);
     }
     MH_DEV uint32_t walk(const DScene &S, Pcg &rng, State &v, WMei &wm) { return vs_walk(S, rng, v.ds, v.ns, wm); }
     MH_DEV uint32_t medium_step(const DScene &S, const IntegratorParams &in, Pcg &rng, State &v, WMei &wm, uint32_t ph,
@@ -1243,7 +1250,7 @@ struct VolMachine {
         return vs_trace_hit(S, in, rng, ph, v, wm, h, r, nc, ns);
     }
     MH_DEV uint32_t post(const DScene &S, const LdsBvh &, const IntegratorParams &in, Pcg &rng, State &v, uint32_t &) {
-        return volpath_post(S, in, rng, v) ? kPhHead : kPhFree;
+        return volpath_post<Ext>(S, in, rng, v) ? kPhHead : kPhFree;
     }
     MH_DEV void end(const DScene &, const LdsBvh &, const IntegratorParams &, float *out, uint64_t plane,
                     uint32_t pid, const State &v, int alpha, uint32_t &, uint32_t &) {
@@ -1251,10 +1258,13 @@ struct VolMachine {
     }
     MH_DEV void finish() {}
 };
+using VolMachine = VolMachineT<true>;
+using VolMachineHg = VolMachineT<false>;   // scenes whose media are all isotropic or HG
 
 struct PvMachine {
     using State = PvState;
     static constexpr bool kPrb = true, kWritesPos = true, kDeferEnd = false, kMergeMed = MH_PV_MERGE != 0;
+    static constexpr bool kPhaseTab = true;
     PvNoHook h;
     MH_DEV PvMachine(const VsBwdArgs &, const LaneMap &, uint32_t) {}
     MH_DEV void init(const DScene &S, const IntegratorParams &in, Pcg &rng, RayT r, State &v, float, float) {
@@ -1346,6 +1356,7 @@ struct PvBwdMachine {
     // the end-of-path log application is a phase of its own (kPhEnd): run
     // when a path ends, it would hold the wave for the few lanes that ended
     static constexpr bool kPrb = true, kWritesPos = false, kDeferEnd = true, kMergeMed = MH_PVB_MERGE != 0;
+    static constexpr bool kPhaseTab = true;
     VsBwdArgs a;
     GradCtx g;
     LaneMap lm;
@@ -1596,7 +1607,10 @@ __host__ __device__ inline uint32_t vs_defer_bytes(const DScene &S) {
 // chains; from global memory each of those is a dependent L2 round trip
 // (~20 per trip), from LDS ~100 cycles.
 __host__ __device__ inline uint32_t vs_media_bytes(const DScene &S) { return (S.n_media * (uint32_t)sizeof(DMedium) + 15u) & ~15u; }
-__host__ __device__ inline uint32_t vs_tab_bytes(const DScene &S) { return ((S.tab_bytes + 15u) & ~15u) + vs_media_bytes(S); }
+// (+ the tabulated phase functions' tables when the launch stages them: DScene::phase_lds_bytes, a multiple of 16)
+__host__ __device__ inline uint32_t vs_tab_bytes(const DScene &S, bool phase = true) {
+    return ((S.tab_bytes + 15u) & ~15u) + vs_media_bytes(S) + (phase ? S.phase_lds_bytes : 0u);
+}
 
 template <class M, bool InLds, bool Pk, bool Tab>
 __global__ void __launch_bounds__(256u, MH_VS_WAVES)
@@ -1612,9 +1626,14 @@ k_vol_sched(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value, uin
         const uint32_t mo = (S0.tab_bytes + 15u) & ~15u;
         uint8_t *mb = reinterpret_cast<uint8_t *>(lds) + mo;
         lds_copy(mb, S0.media, S0.n_media * (uint32_t)sizeof(DMedium));
+        if (M::kPhaseTab && S0.phase_lds_bytes) {
+            uint8_t *pb = mb + vs_media_bytes(S0);
+            lds_copy(pb, S0.phase_tab, S0.phase_lds_bytes);
+            S.phase_tab = reinterpret_cast<const PhaseRec *>(pb);
+        }
         __syncthreads();
         S.media = reinterpret_cast<const DMedium *>(mb);
-        tab = vs_tab_bytes(S0) / 16u;
+        tab = vs_tab_bytes(S0, M::kPhaseTab) / 16u;
     }
     LdsBvh B = stage_bvh<InLds>(S0, lds + tab);
     if (Pk && MH_VS_DEFER) {  // pair records + deferral scratch after the stacks (vs_defer_bytes)
@@ -1867,23 +1886,49 @@ uint32_t vw_blocks(int cus) {
     return std::max<uint32_t>(kVwSeg, (uint32_t)cus * (uint32_t)env::vw_bpc(8) / kVwSeg * kVwSeg);
 }
 
-hipError_t launch_vol_sched(const DScene &S, const IntegratorParams &in, const LaneMap &lm, uint32_t seed_value,
+// the launch's scene: with the phase tables staged (the kernels with the LDS
+// tables only) where plan::phase_lds_bytes finds room beside the launch's
+// dynamic LDS and the static LDS of the kernel instance that stages them (M's
+// <false, true, true>; the runtime's figure, so the machines' arrays may grow).
+// -DMH_PHASE_LDS=0 builds keep the tables in global memory (A/B).
+#ifndef MH_PHASE_LDS
+#define MH_PHASE_LDS 1
+#endif
+template <class M>
+static hipError_t vs_launch_scene(const DScene &S0, bool pk, bool tab, DScene &S) {
+    S = S0;
+    S.phase_lds_bytes = 0;
+    if (!MH_PHASE_LDS || !pk || !tab || !S.phase_tab_bytes) return hipSuccess;
+    hipFuncAttributes fa;
+    hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_vol_sched<M, false, true, true>));
+    if (e != hipSuccess) return e;
+    S.phase_lds_bytes = plan::phase_lds_bytes(S.phase_tab_bytes, lds_bytes(S, 256) + vs_tab_bytes(S) +
+                                                                     vs_defer_bytes(S) + fa.sharedSizeBytes);
+    return hipSuccess;
+}
+
+hipError_t launch_vol_sched(const DScene &S0, const IntegratorParams &in, const LaneMap &lm, uint32_t seed_value,
                             uint64_t n, uint64_t plane, float *out, uint32_t grid, unsigned long long *counters,
                             hipStream_t st, int alpha) {
     if (n == 0) return hipSuccess;
+    const bool pk = vol_packet(S0), tab = vs_tables(S0);
+    DScene S;
+    hipError_t e = in.type == MH_INTEGRATOR_PRBVOLPATH ? vs_launch_scene<PvMachine>(S0, pk, tab, S)
+                                                       : vs_launch_scene<VolMachine>(S0, pk, tab, S);
+    if (e != hipSuccess) return e;
     const size_t sh = lds_bytes(S, 256);
     const bool lds = S.lds_bytes_bvh != 0;
-    const bool pk = vol_packet(S), tab = vs_tables(S);
 #define MH_VS1(Mc, L, P, T)                                                                                   \
     hipLaunchKernelGGL((k_vol_sched<Mc, L, P, T>), dim3(grid), dim3(256), sh + (T ? vs_tab_bytes(S) : 0u) + (P ? vs_defer_bytes(S) : 0u), st, S, \
                        in, lm, seed_value, n, plane, out, counters, work, alpha, VsBwdArgs{})
 #define MH_VS(L, P, T)                                                  \
     do {                                                                \
         if (in.type == MH_INTEGRATOR_PRBVOLPATH) MH_VS1(PvMachine, L, P, T); \
-        else MH_VS1(VolMachine, L, P, T);                               \
+        else if (S.vol_flags & kVolPhaseExt) MH_VS1(VolMachine, L, P, T); \
+        else MH_VS1(VolMachineHg, L, P, T);                             \
     } while (0)
     unsigned long long *work = counters + 32;  // the 8 queue heads of this launch (128 B apart)
-    hipError_t e = hipMemsetAsync(work, 0, 8 * 128, st);
+    e = hipMemsetAsync(work, 0, 8 * 128, st);
     if (e != hipSuccess) return e;
     if (pk && tab) MH_VS(false, true, true);
     else if (pk) MH_VS(false, true, false);
@@ -1932,17 +1977,21 @@ extern "C" int mh_exp_vs_sub(unsigned long long *out, int reset) {
 
 // prbvolpath's single-pass backward on the phase scheduler: n samples of the
 // lane map, gradients into bw.ga's slot buffers (k_prbvol_backward's Mode 2)
-hipError_t launch_vol_sched_bwd(const DScene &S, const IntegratorParams &in, const LaneMap &lm, uint32_t seed_value,
+hipError_t launch_vol_sched_bwd(const DScene &S0, const IntegratorParams &in, const LaneMap &lm, uint32_t seed_value,
                                 uint64_t n, const VsBwdArgs &bw, uint32_t grid, unsigned long long *counters,
                                 hipStream_t st) {
     if (n == 0) return hipSuccess;
     if (in.type != MH_INTEGRATOR_PRBVOLPATH || !bw.main_log || !bw.nee_log || !bw.main_cap || !bw.nee_cap)
         return hipErrorInvalidValue;
+    const bool pk = vol_packet(S0), tab = vs_tables(S0);
+    DScene S;
+    hipError_t e = bw.ga.emitter_off ? vs_launch_scene<PvBwdMachineEm>(S0, pk, tab, S)
+                                     : vs_launch_scene<PvBwdMachine>(S0, pk, tab, S);
+    if (e != hipSuccess) return e;
     const size_t sh = lds_bytes(S, 256);
     const bool lds = S.lds_bytes_bvh != 0;
-    const bool pk = vol_packet(S), tab = vs_tables(S);
     unsigned long long *work = counters + 32;  // the 8 queue heads of this launch (128 B apart)
-    hipError_t e = hipMemsetAsync(work, 0, 8 * 128, st);
+    e = hipMemsetAsync(work, 0, 8 * 128, st);
     if (e != hipSuccess) return e;
 #define MH_VSB1(M, L, P, T)                                                                                    \
     hipLaunchKernelGGL((k_vol_sched<M, L, P, T>), dim3(grid), dim3(256), sh + (T ? vs_tab_bytes(S) : 0u) + (P ? vs_defer_bytes(S) : 0u), \

@@ -44,7 +44,7 @@ def image_channel_names(fmt: int):
     return {PIXEL_RGB: ["R", "G", "B"], PIXEL_Y: ["Y"], PIXEL_XYZ: ["X", "Y", "Z"],
             PIXEL_RGBA: ["R", "G", "B", "A"], PIXEL_YA: ["Y", "A"], PIXEL_XYZA: ["X", "Y", "Z", "A"]}[fmt]
 MEDIUM_HETEROGENEOUS, MEDIUM_HOMOGENEOUS = 0, 1
-PHASE_ISOTROPIC, PHASE_HG = 0, 1
+PHASE_ISOTROPIC, PHASE_HG, PHASE_RAYLEIGH, PHASE_TABULATED = 0, 1, 2, 3
 MEDIUM_NO_EMITTER_SAMPLING, MEDIUM_NO_SPECTRAL_EXTINCTION = 1, 2
 INTEGRATOR_PATH, INTEGRATOR_VOLPATH, INTEGRATOR_PRB, INTEGRATOR_PRBVOLPATH = 0, 1, 2, 3
 # differentiable parameter ids of mh_render_backward (texture index, or kind | medium / emitter)
@@ -143,7 +143,8 @@ EXPORTS = [
     "mh_scene_bvh_info", "mh_render_samples", "mh_scene_update_medium", "mh_trace_preliminary",
     "mh_render_forward", "mh_comm_unique_id", "mh_comm_create", "mh_comm_create_all", "mh_comm_destroy",
     "mh_comm_info", "mh_comm_reduce", "mh_scene_set_comm", "mh_scene_synchronize", "mh_render_sharded",
-    "mh_render_backward_sharded", "mh_scene_update_emitter",
+    "mh_render_backward_sharded", "mh_scene_update_emitter", "mh_scene_set_phase_table", "mh_phase_sample",
+    "mh_phase_eval",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -184,6 +185,9 @@ def lib():
     L.mh_scene_update_texture.argtypes = [vp, u32, PF, u64]
     L.mh_scene_update_medium.argtypes = [vp, u32, vp, vp, vp, u64, u32]
     L.mh_scene_update_emitter.argtypes = [vp, u32, PF]
+    L.mh_scene_set_phase_table.argtypes = [vp, u32, u32, PF, PF]
+    L.mh_phase_sample.argtypes = [vp, u32, u64, vp, vp, vp, u32]
+    L.mh_phase_eval.argtypes = [vp, u32, u64, vp, vp, u32]
     L.mh_render.argtypes = [vp, C.POINTER(Integrator), u32, u32, u32, u32, vp, u32, C.POINTER(Stats)]
     L.mh_develop.argtypes = [vp, vp, vp, u32]
     L.mh_render_samples.argtypes = [vp, C.POINTER(Integrator), u32, u32, u32, u32, vp, u32]

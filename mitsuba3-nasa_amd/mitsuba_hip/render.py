@@ -88,6 +88,8 @@ class SceneParameters:
                 v = torch.tensor(list(scene.medium(idx).albedo), dtype=torch.float32)
             elif kind == "emitter_radiance":
                 v = torch.tensor(list(scene.emitter(idx).radiance), dtype=torch.float32)
+            elif kind == "phase_table":
+                v = torch.from_numpy(scene.phase_tables[idx][1].copy())
             else:
                 continue
             if device is not None:
@@ -128,6 +130,9 @@ class SceneParameters:
     def param_id(self, k) -> int:
         """mh_render_backward parameter id (include/mitsuba_hip.h MH_PARAM_*)."""
         kind, idx = self._kind[k]
+        if kind == "phase_table":
+            raise A.MitsubaHipError(f"'{k}' can be updated but is not differentiable in the hip_ad_rgb variant "
+                                    "(phase function gradients are not implemented)")
         if kind in ("grid", "medium_sigma_t"):
             return A.PARAM_MEDIUM_SIGMA_T | idx
         if kind == "medium_albedo":
@@ -154,6 +159,12 @@ class SceneParameters:
                 self.scene.emitter(idx).radiance[:] = [float(x) for x in arr]
                 for h in self.scene._handles.values():
                     A.check(L.mh_scene_update_emitter(h, idx, arr.ctypes.data_as(A.PF)))
+            elif kind == "phase_table":
+                # tabphase.cpp:86-88 parameters_changed -> m_distr.update()
+                from .scene import phase_table
+                self.scene.phase_tables[idx] = phase_table(self.scene.phase_tables[idx][0], arr)
+                for h in self.scene._handles.values():
+                    self.scene.upload_phase_table(h, idx)
             elif kind in ("grid", "medium_sigma_t", "medium_albedo"):
                 m = self.scene.medium(idx)
                 if kind == "grid":

@@ -165,6 +165,44 @@ def _to_transform(v) -> Transform4f:
     return Transform4f(np.asarray(v, dtype=np.float64).reshape(4, 4))
 
 
+def phase_table(cost, values):
+    """The 'cost' / 'values' of a tabphase (phase/tabphase.cpp:44-75: strings
+    of comma / space separated floats; arrays are accepted too) as float32
+    arrays, checked as IrregularContinuousDistribution::compute_cdf_scalar
+    (core/distr_1d.h:916-978) and mh_scene_set_phase_table check them."""
+    def floats(v, what):
+        if v is None:
+            raise RuntimeError(f'Property "{what}" has not been specified!')
+        if isinstance(v, str):
+            out = []
+            for tok in v.replace(",", " ").split():
+                try:
+                    out.append(float(tok))
+                except ValueError:
+                    raise RuntimeError(f"Could not parse floating point value '{tok}'") from None
+            return np.asarray(out, np.float32)
+        return np.ascontiguousarray(np.asarray(v, np.float64).reshape(-1).astype(np.float32))
+    c, v = floats(cost, "cost"), floats(values, "values")
+    if c.size != v.size:
+        raise RuntimeError("TabulatedPhaseFunction: 'cost' and 'values' parameters must have the same size!")
+    if c.size < 2:
+        raise RuntimeError("IrregularContinuousDistribution: needs at least two entries!")
+    if c.size > 65536:
+        raise RuntimeError("hip_ad_rgb: tabphase: more than 65536 entries")
+    if not (np.all(np.isfinite(c)) and np.all(np.isfinite(v))):
+        raise RuntimeError("hip_ad_rgb: tabphase: entries must be finite")
+    if not np.all(c[1:] > c[:-1]):
+        raise RuntimeError("IrregularContinuousDistribution: node positions must be strictly increasing!")
+    if c[0] < -1.0 or c[-1] > 1.0:
+        raise RuntimeError("hip_ad_rgb: tabphase: 'cost' must lie in [-1, 1]")
+    if np.any(v < 0):
+        raise RuntimeError("IrregularContinuousDistribution: entries must be non-negative!")
+    mass = 0.5 * (c[1:].astype(np.float64) - c[:-1]) * (v[1:].astype(np.float64) + v[:-1])
+    if not np.any(mass > 0):
+        raise RuntimeError("IrregularContinuousDistribution: no probability mass found!")
+    return c, v
+
+
 class _Builder:
     """Accumulates flattened plugin records."""
 
@@ -190,6 +228,7 @@ class _Builder:
         self.medium_ids: Dict[str, int] = {}
         self.grids: List[np.ndarray] = []
         self.n_grid = 0
+        self.phase_tables: Dict[int, Any] = {}   # medium index -> (cost, values) of a tabphase
         self.environment = A.INVALID
         self.bbox_min = np.full(3, np.inf, np.float32)   # Scene::bbox() over the shapes
         self.bbox_max = np.full(3, -np.inf, np.float32)
@@ -306,6 +345,21 @@ class _Builder:
             m.phase, m.g = A.PHASE_HG, float(np.float32(g))
         elif ph.get("type") == "isotropic":
             m.phase, m.g = A.PHASE_ISOTROPIC, 0.0
+        elif ph.get("type") == "rayleigh":
+            # rayleigh.cpp:40-47; with depolarization the phase value differs
+            # from the sampling density (rayleigh.cpp:79-84 vs :50-52)
+            rho = float(ph.get("depolarization", 0.0))
+            if rho < 0.0 or rho >= 1.0:
+                raise RuntimeError("Depolarization factor must be between 0 and 1!")
+            if rho != 0.0:
+                raise RuntimeError("hip_ad_rgb: the rayleigh phase function is supported with depolarization = 0 "
+                                   "only: otherwise its value differs from its sampling density and the sampling "
+                                   "weight is not 1, which the volumetric integrators here do not carry")
+            m.phase, m.g = A.PHASE_RAYLEIGH, 0.0
+        elif ph.get("type") == "tabphase":
+            m.phase, m.g = A.PHASE_TABULATED, 0.0
+            self.phase_tables[len(self.media)] = phase_table(ph.get("cost"), ph.get("values"))
+            self.params[name + ".phase_function.values"] = ("phase_table", len(self.media))
         else:
             raise RuntimeError(f'Phase function plugin "{ph.get("type")}" is not available in the hip_ad_rgb variant')
         m.flags = ((0 if spec.get("sample_emitters", True) else A.MEDIUM_NO_EMITTER_SAMPLING) |
@@ -556,6 +610,7 @@ class Scene:
         self.faces = cat(b.faces, 3, np.uint32)
         self.texels = cat(b.texels, 1, np.float32)
         self.grid = cat(b.grids, 1, np.float32)
+        self.phase_tables = b.phase_tables
         d = A.SceneDesc()
         d.abi_version = A.ABI_VERSION
         d.sensor = sensor
@@ -625,11 +680,18 @@ class Scene:
             h = C.c_void_p()
             A.check(L.mh_scene_create(C.byref(self.desc), device, None, C.byref(h)))
             self._handles[device] = h
+            for idx in self.phase_tables:
+                self.upload_phase_table(h, idx)
             self._streams[device] = None
         if stream is not None and self._streams.get(device) != stream:
             A.check(A.lib().mh_scene_set_stream(h, C.c_void_p(stream) if stream else None))
             self._streams[device] = stream
         return h
+
+    def upload_phase_table(self, h, idx: int):
+        """mh_scene_set_phase_table of medium `idx` (a tabphase) on handle `h`."""
+        c, v = self.phase_tables[idx]
+        A.check(A.lib().mh_scene_set_phase_table(h, idx, c.size, c.ctypes.data_as(A.PF), v.ctypes.data_as(A.PF)))
 
     def release(self):
         if self._handles:

@@ -3,7 +3,11 @@
 medium + HG, 256x256 @ 64 spp, one MI355X.  --integrator prbvolpath times the
 §8(f) extension instead: one step = prbvolpath forward + render_backward wrt
 the sigma_t grid and the albedo.  Prints one JSON line (not the driver's
-bench line: bench.py measures BASELINE.json's headline metric)."""
+bench line: bench.py measures BASELINE.json's headline metric).
+--phase replaces the medium's HG (g = 0.85) by `rayleigh`, or by `tab`: the same
+HG tabulated for `tabphase` on 1,801 cosines of a grid uniform in angle (0.1
+degree), the size of a Mie table; the difference to hg is the cost of the
+table searches.  The CPU oracle has neither, so these runs skip its baseline."""
 import argparse
 import json
 import os
@@ -12,6 +16,19 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "mitsuba3-nasa_amd"), os.path.join(ROOT, "tests")]
+
+
+def phase_spec(name):
+    if name == "rayleigh":
+        return {"type": "rayleigh"}
+    if name == "tab":
+        import numpy as np
+        c = np.cos(np.deg2rad(np.linspace(180.0, 0.0, 1801)))
+        c[0], c[-1] = -1.0, 1.0
+        g = 0.85
+        return {"type": "tabphase", "cost": c,
+                "values": (1 - g * g) / (4 * np.pi * (1 + g * g - 2 * g * c) ** 1.5)}
+    return {"type": "hg", "g": 0.85}
 
 
 def main():
@@ -28,7 +45,10 @@ def main():
                     help="prbvolpath: MH_FLAG_DETERMINISTIC backward (int64 fixed-point grid + albedo gradients)")
     ap.add_argument("--overlap", action="store_true",
                     help="prbvolpath: forward || backward on two scene handles and streams (grad_in is constant)")
+    ap.add_argument("--phase", default="hg", choices=["hg", "rayleigh", "tab"],
+                    help="the medium's phase function: hg (g = 0.85), rayleigh, or that hg as an 1,801-node tabphase")
     a = ap.parse_args()
+    a.no_cpu = a.no_cpu or a.phase != "hg"   # the oracle has only isotropic and hg
     import torch
     import mitsuba_hip as mi
     from mitsuba_hip import _abi as A
@@ -37,6 +57,7 @@ def main():
     grid = mi.fbm_grid(a.grid)
     d = mi.volume_cube(a.res, a.res, a.spp, grid=grid)
     d["integrator"]["type"] = a.integrator
+    d["medium1"]["phase"] = phase_spec(a.phase)
     if a.no_nee:
         d["medium1"]["sample_emitters"] = False
     scene = mi.load_dict(d)
@@ -59,7 +80,7 @@ def main():
            "ms_per_render": round(dt * 1e3, 3), "kernel_ms": round(sum(ks) / len(ks), 3),
            "rays_closest_per_sample": round(st.rays_closest / n, 3),
            "rays_shadow_per_sample": round(st.rays_shadow / n, 3),
-           "config": {"film": f"{a.res}x{a.res}", "spp": a.spp, "grid": f"{a.grid}^3 fBm",
+           "config": {"film": f"{a.res}x{a.res}", "spp": a.spp, "grid": f"{a.grid}^3 fBm", "phase": a.phase,
                       "scene_load_s": round(t_load, 2)}}
     if not a.no_cpu:
         import oracle_py as O
@@ -101,6 +122,7 @@ def bench_prbvolpath(a, mi, A, scene, t_load):
         from mitsuba_hip import distributed as D
         d = mi.volume_cube(a.res, a.res, a.spp, grid=mi.fbm_grid(a.grid))
         d["integrator"]["type"] = a.integrator
+        d["medium1"]["phase"] = phase_spec(a.phase)
         scene_f = mi.load_dict(d)  # the forward's own handle
         dev = torch.device("cuda:0")
         run = D.PairRunner((torch.cuda.Stream(dev), torch.cuda.Stream(dev)), dev)
@@ -130,7 +152,7 @@ def bench_prbvolpath(a, mi, A, scene, t_load):
            "deterministic": a.deterministic, "overlap": a.overlap, "bwd_subphases": sub,
            "fwd_rays_closest_per_sample": round(sf.rays_closest / n, 3),
            "fwd_rays_shadow_per_sample": round(sf.rays_shadow / n, 3),
-           "config": {"film": f"{a.res}x{a.res}", "spp": a.spp, "grid": f"{a.grid}^3 fBm",
+           "config": {"film": f"{a.res}x{a.res}", "spp": a.spp, "grid": f"{a.grid}^3 fBm", "phase": a.phase,
                       "scene_load_s": round(t_load, 2)}}
     if not a.no_cpu:
         import numpy as np

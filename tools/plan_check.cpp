@@ -176,6 +176,12 @@ int main() {
     backward("bwd_envdet_rgb_replay", rgb, {{"MH_DETERMINISTIC", "1"}, {"MH_PRB_REPLAY", "1"}});
     printf("{\"case\": \"bmp_record_cap\", \"depth_31\": %llu, \"depth_4096\": %llu}\n",
            (unsigned long long)plan::bmp_record_cap(31), (unsigned long long)plan::bmp_record_cap(4096));
+    // the phase tables' LDS residency: a 28,848-byte table (1,801 nodes + 2 records) beside other LDS
+    printf("{\"case\": \"phase_lds\", \"fits_exactly\": %u, \"one_over\": %u, \"no_table\": %u, \"alone\": %u, "
+           "\"alone_over\": %u, \"huge_other\": %u}\n",
+           plan::phase_lds_bytes(28848, 65536 - 28848), plan::phase_lds_bytes(28848, 65536 - 28848 + 1),
+           plan::phase_lds_bytes(0, 1024), plan::phase_lds_bytes(65536, 0), plan::phase_lds_bytes(65552, 0),
+           plan::phase_lds_bytes(16, ~0ull - 8));
     // prbvolpath
     const plan::Facts pvp = facts(PVP, 8, 16, 16, 8);
     backward("bwd_pvp", pvp);
