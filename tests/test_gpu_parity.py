@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import oracle_py as O
+import vol_cases as VC
 
 pytestmark = pytest.mark.gpu
 
@@ -248,10 +249,7 @@ def _vol_floor_scene(mi, w=24, h=20, spp=8, **kw):
     kw.setdefault("grid", mi.fbm_grid(16))
     kw.setdefault("scale", 4.0)
     d = mi.volume_cube(w, h, spp, **kw)
-    T = mi.Transform4f
-    d["floor"] = {"type": "rectangle",
-                  "to_world": T.translate([0, -1.2, 0]) @ T.rotate([1, 0, 0], -90) @ T.scale([3, 3, 3]),
-                  "bsdf": {"type": "diffuse", "reflectance": {"type": "rgb", "value": [0.6, 0.5, 0.4]}}}
+    d["floor"] = VC.floor(mi)
     return mi.load_dict(d)
 
 
@@ -332,10 +330,7 @@ def _pvp_scene(mi, w=24, h=20, spp=8, floor=True, pixel_format=None, **kw):
         d["sensor"]["film"]["pixel_format"] = pixel_format
     d["integrator"] = {"type": "prbvolpath", "max_depth": kw.get("max_depth", 6), "rr_depth": 5}
     if floor:
-        T = mi.Transform4f
-        d["floor"] = {"type": "rectangle",
-                      "to_world": T.translate([0, -1.2, 0]) @ T.rotate([1, 0, 0], -90) @ T.scale([3, 3, 3]),
-                      "bsdf": {"type": "diffuse", "reflectance": {"type": "rgb", "value": [0.6, 0.5, 0.4]}}}
+        d["floor"] = VC.floor(mi)
     return mi.load_dict(d)
 
 
