@@ -83,8 +83,11 @@ enum { MH_PIXEL_RGB = 0, MH_PIXEL_Y = 1, MH_PIXEL_XYZ = 2, MH_PIXEL_RGBA = 3, MH
        MH_PIXEL_XYZA = 5 };
 enum { MH_MEDIUM_HETEROGENEOUS = 0, MH_MEDIUM_HOMOGENEOUS = 1 };
 /* isotropic.cpp, hg.cpp, rayleigh.cpp (depolarization 0 only: mh_medium::g must
- * be 0 for it), tabphase.cpp (the table comes from mh_scene_set_phase_table) */
-enum { MH_PHASE_ISOTROPIC = 0, MH_PHASE_HG = 1, MH_PHASE_RAYLEIGH = 2, MH_PHASE_TABULATED = 3 };
+ * be 0 for it), tabphase.cpp (the table comes from mh_scene_set_phase_table),
+ * blendphase.cpp (two children and weight_0 come from mh_scene_set_phase_blend;
+ * mh_medium::g is not read) */
+enum { MH_PHASE_ISOTROPIC = 0, MH_PHASE_HG = 1, MH_PHASE_RAYLEIGH = 2, MH_PHASE_TABULATED = 3,
+       MH_PHASE_BLEND = 4 };
 enum { MH_MEDIUM_NO_EMITTER_SAMPLING = 1u,        /* medium.cpp:29 sample_emitters = false */
        MH_MEDIUM_NO_SPECTRAL_EXTINCTION = 2u };   /* heterogeneous.cpp:161 has_spectral_extinction = false */
 enum { MH_INTEGRATOR_PATH = 0, MH_INTEGRATOR_VOLPATH = 1, MH_INTEGRATOR_PRB = 2,
@@ -340,6 +343,54 @@ int mh_scene_set_phase_table(mh_scene *scene, uint32_t medium, uint32_t n, const
                              const float *values);
 
 /*
+ * The phase function of a MH_PHASE_BLEND medium (BlendPhaseFunction,
+ * src/phase/blendphase.cpp) with two children: child 0 weighted by
+ * w = clamp(weight_0, 0, 1) at the interaction point, child 1 by 1 - w
+ * (:196-200, :219).  eval_pdf is w p0 + (1 - w) p1 (:246-251).  sample takes
+ * child 0 when 0 < sample1 < w and child 1 when w < sample1 < 1 (strict: sample1
+ * == 0 or == w selects nothing and the path ends) and returns that child's
+ * direction and that child's pdf, not the mixture's (:176-188); the integrators
+ * carry it into MIS as the reference does.
+ *   phase[i], g[i] : MH_PHASE_ISOTROPIC, _HG (asymmetry g), _RAYLEIGH (g must be
+ *                    0) or _TABULATED (its table: mh_scene_set_phase_blend_table)
+ *   weight_0       : the constant `weight` when grid_res is all 0; else a
+ *                    one-channel grid (trilinear, clamp: src/volumes/grid.cpp) of
+ *                    grid_res = (x, y, z) texels, grid_data[(z * res_y + y) *
+ *                    res_x + x] (a host pointer, copied by the call), with
+ *                    grid_to_local the 3x4 row-major world -> [0, 1]^3 transform;
+ *                    independent of the medium's sigma_t grid.
+ */
+typedef struct mh_phase_blend {
+    uint32_t phase[2];
+    float g[2];
+    float weight;
+    uint32_t grid_res[3];
+    float grid_to_local[12];
+    const float *grid_data;
+} mh_phase_blend;
+/*
+ * Attach `blend` to medium `medium` (call it after mh_scene_create and before
+ * the first render; a second call replaces it, keeping the table of a child
+ * that stays tabulated).  Then give every MH_PHASE_TABULATED child its table
+ * with mh_scene_set_phase_blend_table(child = 0 or 1), which checks and builds
+ * it exactly as mh_scene_set_phase_table does.  Until a blend medium has its
+ * blend and its tabulated children their tables, mh_render / mh_render_samples
+ * / mh_render_backward / mh_render_forward and the phase queries return
+ * MH_ERR_INVALID_ARGUMENT before any launch.
+ * mh_scene_update_phase_blend_weight replaces weight_0's values: n = 1 (the
+ * constant) or n = x * y * z (the grid, in grid_data's order; host pointer).
+ * All three: MH_ERR_INVALID_ARGUMENT for a NULL argument, an index out of
+ * bounds, a medium that is not MH_PHASE_BLEND, a child type or parameter out
+ * of range, non-finite weights or a size mismatch; ordered on the scene's
+ * stream.  Gradients with respect to the weight or the children are not
+ * implemented.
+ */
+int mh_scene_set_phase_blend(mh_scene *scene, uint32_t medium, const mh_phase_blend *blend);
+int mh_scene_set_phase_blend_table(mh_scene *scene, uint32_t medium, uint32_t child, uint32_t n,
+                                   const float *cost, const float *values);
+int mh_scene_update_phase_blend_weight(mh_scene *scene, uint32_t medium, const float *data, uint64_t n);
+
+/*
  * Forward render into the un-developed film storage: RGBW (H*W*4 floats), or
  * R G B A W (H*W*5) when the film has an alpha channel (MH_PIXEL_RGBA / YA /
  * XYZA; hdrfilm.cpp:327-330 base_ch = 5).  A sample's alpha is 1 where the
@@ -452,6 +503,20 @@ int mh_trace_shadow(mh_scene *scene, uint64_t n, const float *rays, uint32_t *oc
 int mh_phase_sample(mh_scene *scene, uint32_t medium, uint64_t n, const float *u, float *wo, float *pdf,
                     uint32_t flags);
 int mh_phase_eval(mh_scene *scene, uint32_t medium, uint64_t n, const float *wo, float *value, uint32_t flags);
+/*
+ * The same queries with PhaseFunction::sample's sample1 and the interaction
+ * point, which a blend reads (the child selection; weight_0 at the point, looked
+ * up once per item); every other phase function ignores both and returns what
+ * the calls above return.  On a MH_PHASE_BLEND medium the calls above return
+ * MH_ERR_INVALID_ARGUMENT and name these.
+ *   mh_phase_sample_at : u = SoA u1[n] u2x[n] u2y[n], pos = SoA x[n] y[n] z[n]
+ *                        (world) -> wo = SoA x[n] y[n] z[n], pdf[n]
+ *   mh_phase_eval_at   : wo = SoA x[n] y[n] z[n], pos as above -> value[n]
+ */
+int mh_phase_sample_at(mh_scene *scene, uint32_t medium, uint64_t n, const float *u, const float *pos, float *wo,
+                       float *pdf, uint32_t flags);
+int mh_phase_eval_at(mh_scene *scene, uint32_t medium, uint64_t n, const float *wo, const float *pos, float *value,
+                     uint32_t flags);
 
 /* BVH introspection (host): #nodes, #primitives, max depth. */
 int mh_scene_bvh_info(mh_scene *scene, uint32_t *n_nodes, uint32_t *n_prims, uint32_t *depth);

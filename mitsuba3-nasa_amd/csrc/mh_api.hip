@@ -122,6 +122,17 @@ struct mh_scene {
         texcoords, faces, texels, media, grid;
     DevBuf phase_tab;  // the tabulated phase functions' tables, one after the other (DScene::phase_tab)
     std::vector<std::vector<PhaseRec>> h_phase_tabs;  // per medium (empty: none set)
+    // a MH_PHASE_BLEND medium's phase function (mh_scene_set_phase_blend): its device record and its tabulated
+    // children's tables (they join phase_tab) and its weight grid in the bricked layout (it joins `grid`,
+    // after the grid_floats floats of the media's own grids)
+    struct BlendHost {
+        bool set = false;
+        DBlend rec{};
+        std::vector<PhaseRec> tab[2];
+        std::vector<float> grid;
+    };
+    std::vector<BlendHost> h_blends;  // per medium
+    size_t grid_floats = 0;
     DevBuf work, film_tmp, film4, alpha_px, counters, grad_meta, tmp_a, tmp_b, tmp_c, tmp_d, tmp_e, weights_tmp;
     std::vector<uint8_t> meta_host;  // the bytes last uploaded to grad_meta (upload_slots)
     DevBuf wf_ws, wf_ctr;  // wavefront state (SoA) and per-chunk/bounce queue counters
@@ -357,7 +368,7 @@ int mh_scene_create(const mh_scene_desc *desc, int device, void *stream, mh_scen
             return fail(MH_ERR_UNSUPPORTED, "mh_scene_create: volume grid above 2^32 texels");
         if (a.phase == MH_PHASE_HG && !(a.g > -1.f && a.g < 1.f))
             return fail(MH_ERR_INVALID_ARGUMENT, "The asymmetry parameter must lie in the interval (-1, 1)!");
-        if (a.phase > MH_PHASE_TABULATED)
+        if (a.phase > MH_PHASE_BLEND)
             return fail(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: unknown phase function");
         // rayleigh.cpp:124-126 returns a value that differs from the pdf when
         // depolarization != 0 (the sampling weight is then not 1)
@@ -382,6 +393,8 @@ int mh_scene_create(const mh_scene_desc *desc, int device, void *stream, mh_scen
     s->h_media.assign(desc->media, desc->media + desc->n_media);
     s->h_dmedia = meds;
     s->h_phase_tabs.assign(desc->n_media, {});
+    s->h_blends.assign(desc->n_media, {});
+    s->grid_floats = bricked.size();
     s->n_media = desc->n_media;
     if (desc->sensor.medium != MH_INVALID && desc->sensor.medium >= desc->n_media)
         return fail(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: sensor medium index out of bounds");
@@ -464,6 +477,8 @@ int mh_scene_create(const mh_scene_desc *desc, int device, void *stream, mh_scen
     for (uint32_t i = 0; i < desc->n_media; ++i)
         if (desc->media[i].phase == MH_PHASE_RAYLEIGH || desc->media[i].phase == MH_PHASE_TABULATED)
             S.vol_flags |= kVolPhaseExt;
+        else if (desc->media[i].phase == MH_PHASE_BLEND)
+            S.vol_flags |= kVolPhaseBlend;   // nothing renders until its blend is attached (check_phase_tables)
     S.n_shapes = desc->n_shapes;
     S.n_bsdfs = desc->n_bsdfs;
     S.n_textures = desc->n_textures;
@@ -701,17 +716,13 @@ int mh_scene_update_medium(mh_scene *s, uint32_t medium, const float *albedo, co
 // ::compute_cdf_scalar builds (distr_1d.h:916-978) -- the interval integrals
 // accumulated in double and stored as float, the first and last interval with
 // positive mass, integral = cdf[valid.y], normalization = 1 / integral -- in
-// the PhaseRec layout (mh_device.hpp).  All tables share one device buffer;
-// the media records carry offset, size and the valid intervals.
-int mh_scene_set_phase_table(mh_scene *s, uint32_t medium, uint32_t n, const float *cost, const float *values) {
-    const char *fn = "mh_scene_set_phase_table: ";
+// the PhaseRec layout (mh_device.hpp).  valid = first | last << 16.
+static int build_phase_table(const char *fn, uint32_t n, const float *cost, const float *values,
+                             std::vector<PhaseRec> &tab, uint32_t &valid) {
     auto bad = [&](const char *why) { return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + why); };
-    if (!s || !cost || !values) return bad("NULL argument");
-    if (medium >= s->n_media) return bad("medium index out of bounds");
-    if (s->h_dmedia[medium].phase != MH_PHASE_TABULATED) return bad("the medium's phase function is not MH_PHASE_TABULATED");
     if (n < 2) return bad("IrregularContinuousDistribution: needs at least two entries!");
     if (n > 65536) return bad("more than 65536 entries");
-    std::vector<PhaseRec> tab((size_t)n + 2);
+    tab.assign((size_t)n + 2, PhaseRec{});
     uint32_t first = MH_INVALID, last = MH_INVALID;
     double integral = 0.;
     for (uint32_t i = 0; i < n; ++i) {
@@ -739,75 +750,276 @@ int mh_scene_set_phase_table(mh_scene *s, uint32_t medium, uint32_t n, const flo
     if (!(total > 0.f) || !std::isfinite(1.f / total)) return bad("the table's integral is not a normal float");
     tab[0] = PhaseRec{total, 1.f / total, cost[0], cost[n - 1]};
     tab[1 + n] = PhaseRec{std::numeric_limits<float>::infinity(), 0.f, total, total};
+    valid = first | (last << 16);
+    return MH_OK;
+}
+
+// The scene's phase data on the device from its (edited) host copies: all
+// tables -- the tabulated media's and the blends' tabulated children's -- and
+// the blends' records (each ahead of its children's tables) in one buffer, the
+// media records with their offsets into it, and, when
+// `regrid`, the grid buffer rebuilt as the media's own grids followed by the
+// blends' weight grids.  Everything is built aside and becomes the scene's only
+// after the last HIP call has succeeded: a failure leaves the old buffers and
+// the records that point into them in place.
+static int commit_phase_data(mh_scene *s, const char *fn, std::vector<DMedium> &media,
+                             std::vector<std::vector<PhaseRec>> &tabs, std::vector<mh_scene::BlendHost> &blends,
+                             bool regrid) {
     MH_HIP(hipSetDevice(s->device));
     MH_HIP(hipStreamSynchronize(s->stream));  // earlier calls may still read the old tables
-    // the new media records and the concatenated tables are built aside and
-    // become the scene's only after the last HIP call has succeeded
-    std::vector<DMedium> media = s->h_dmedia;
     std::vector<PhaseRec> all;
+    uint64_t grid_total = s->grid_floats;
     for (uint32_t m = 0; m < s->n_media; ++m) {
-        const std::vector<PhaseRec> &t = m == medium ? tab : s->h_phase_tabs[m];
-        if (t.empty()) continue;
         DMedium &b = media[m];
-        b.tab_offset = (uint32_t)all.size();
-        b.tab_n = (uint32_t)t.size() - 2u;
-        if (m == medium) b.tab_valid = first | (last << 16);
-        all.insert(all.end(), t.begin(), t.end());
+        if (!tabs[m].empty()) {
+            b.tab_offset = (uint32_t)all.size();
+            b.tab_n = (uint32_t)tabs[m].size() - 2u;
+            all.insert(all.end(), tabs[m].begin(), tabs[m].end());
+        }
+        if (b.phase != MH_PHASE_BLEND) continue;
+        mh_scene::BlendHost &h = blends[m];
+        bool ready = h.set;
+        const size_t at = all.size();
+        if (h.set) all.resize(at + kBlendRecs);   // its DBlend: filled in below, once the children's offsets are known
+        for (int c = 0; c < 2; ++c) {
+            h.rec.tab_offset[c] = h.rec.tab_n[c] = 0;
+            if (!h.set || h.rec.phase[c] != MH_PHASE_TABULATED) continue;
+            if (h.tab[c].empty()) { ready = false; continue; }
+            h.rec.tab_offset[c] = (uint32_t)all.size();
+            h.rec.tab_n[c] = (uint32_t)h.tab[c].size() - 2u;
+            all.insert(all.end(), h.tab[c].begin(), h.tab[c].end());
+        }
+        b.tab_offset = (uint32_t)at;
+        b.tab_n = ready ? 1u : 0u;   // attached: check_phase_tables
+        if (regrid && h.set && h.rec.has_grid) {
+            h.rec.grid_offset = grid_total;
+            grid_total += h.grid.size();
+        }
+        if (h.set) memcpy(static_cast<void *>(&all[at]), &h.rec, sizeof(DBlend));
     }
-    // a buffer of its own: a failure leaves the old tables and the records that point into them in place
-    DevBuf buf;
-    hipError_t e = upload(buf, all.data(), all.size(), s->stream);
+    if (all.size() * sizeof(PhaseRec) >= (1ull << 32))
+        return set_error(MH_ERR_UNSUPPORTED, std::string(fn) + "the phase tables exceed 4 GiB");
+    DevBuf tab_buf, grid_buf;
+    hipError_t e = upload(tab_buf, all.data(), all.size(), s->stream);
+    if (e == hipSuccess && regrid) {
+        e = grid_buf.alloc(std::max<uint64_t>(grid_total, 4) * sizeof(float));
+        if (e == hipSuccess && s->grid_floats)
+            e = hipMemcpyAsync(grid_buf.ptr, s->grid.ptr, s->grid_floats * sizeof(float), hipMemcpyDeviceToDevice, s->stream);
+        for (uint32_t m = 0; m < s->n_media && e == hipSuccess; ++m)
+            if (blends[m].set && blends[m].rec.has_grid)
+                e = hipMemcpyAsync(grid_buf.as<float>() + blends[m].rec.grid_offset, blends[m].grid.data(),
+                                   blends[m].grid.size() * sizeof(float), hipMemcpyHostToDevice, s->stream);
+    }
     if (e == hipSuccess)
         e = hipMemcpyAsync(s->media.ptr, media.data(), sizeof(DMedium) * s->n_media, hipMemcpyHostToDevice, s->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
     if (e != hipSuccess) {
-        buf.release();
+        tab_buf.release();
+        grid_buf.release();
         return set_error(MH_ERR_HIP, std::string(fn) + hipGetErrorString(e));
     }
     s->phase_tab.release();
-    s->phase_tab = buf;
-    s->h_phase_tabs[medium] = std::move(tab);
+    s->phase_tab = tab_buf;
+    if (regrid) {
+        s->grid.release();
+        s->grid = grid_buf;
+        s->S.grid = s->grid.as<float>();
+    }
     s->h_dmedia = std::move(media);
+    s->h_phase_tabs = std::move(tabs);
+    s->h_blends = std::move(blends);
     s->S.phase_tab = s->phase_tab.as<PhaseRec>();
     s->S.phase_tab_bytes = (uint32_t)(all.size() * sizeof(PhaseRec));
     return MH_OK;
 }
 
-// a tabulated medium without its table: the kernels would read a null table
+int mh_scene_set_phase_table(mh_scene *s, uint32_t medium, uint32_t n, const float *cost, const float *values) {
+    const char *fn = "mh_scene_set_phase_table: ";
+    auto bad = [&](const char *why) { return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + why); };
+    if (!s || !cost || !values) return bad("NULL argument");
+    if (medium >= s->n_media) return bad("medium index out of bounds");
+    if (s->h_dmedia[medium].phase != MH_PHASE_TABULATED) return bad("the medium's phase function is not MH_PHASE_TABULATED");
+    std::vector<PhaseRec> tab;
+    uint32_t valid = 0;
+    if (int rc = build_phase_table(fn, n, cost, values, tab, valid)) return rc;
+    std::vector<DMedium> media = s->h_dmedia;
+    std::vector<std::vector<PhaseRec>> tabs = s->h_phase_tabs;
+    std::vector<mh_scene::BlendHost> blends = s->h_blends;
+    tabs[medium] = std::move(tab);
+    media[medium].tab_valid = valid;
+    return commit_phase_data(s, fn, media, tabs, blends, false);
+}
+
+int mh_scene_set_phase_blend_table(mh_scene *s, uint32_t medium, uint32_t child, uint32_t n, const float *cost,
+                                   const float *values) {
+    const char *fn = "mh_scene_set_phase_blend_table: ";
+    auto bad = [&](const char *why) { return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + why); };
+    if (!s || !cost || !values) return bad("NULL argument");
+    if (medium >= s->n_media) return bad("medium index out of bounds");
+    if (child > 1) return bad("child index out of bounds (a blend has two children)");
+    if (s->h_dmedia[medium].phase != MH_PHASE_BLEND) return bad("the medium's phase function is not MH_PHASE_BLEND");
+    if (!s->h_blends[medium].set) return bad("the medium has no blend yet (call mh_scene_set_phase_blend first)");
+    if (s->h_blends[medium].rec.phase[child] != MH_PHASE_TABULATED) return bad("the child is not MH_PHASE_TABULATED");
+    std::vector<PhaseRec> tab;
+    uint32_t valid = 0;
+    if (int rc = build_phase_table(fn, n, cost, values, tab, valid)) return rc;
+    std::vector<DMedium> media = s->h_dmedia;
+    std::vector<std::vector<PhaseRec>> tabs = s->h_phase_tabs;
+    std::vector<mh_scene::BlendHost> blends = s->h_blends;
+    blends[medium].tab[child] = std::move(tab);
+    blends[medium].rec.tab_valid[child] = valid;
+    return commit_phase_data(s, fn, media, tabs, blends, false);
+}
+
+// a weight grid's n values: finite
+static bool all_finite(const float *v, uint64_t n) {
+    for (uint64_t i = 0; i < n; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+int mh_scene_set_phase_blend(mh_scene *s, uint32_t medium, const mh_phase_blend *b) {
+    const char *fn = "mh_scene_set_phase_blend: ";
+    auto bad = [&](const char *why) { return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + why); };
+    if (!s || !b) return bad("NULL argument");
+    if (medium >= s->n_media) return bad("medium index out of bounds");
+    if (s->h_dmedia[medium].phase != MH_PHASE_BLEND) return bad("the medium's phase function is not MH_PHASE_BLEND");
+    for (int c = 0; c < 2; ++c) {
+        if (b->phase[c] > MH_PHASE_TABULATED)
+            return bad("a child must be MH_PHASE_ISOTROPIC, MH_PHASE_HG, MH_PHASE_RAYLEIGH or MH_PHASE_TABULATED "
+                       "(a nested blend is not supported)");
+        if (b->phase[c] == MH_PHASE_HG && !(b->g[c] > -1.f && b->g[c] < 1.f))
+            return bad("The asymmetry parameter must lie in the interval (-1, 1)!");
+        if (b->phase[c] == MH_PHASE_RAYLEIGH && b->g[c] != 0.f)
+            return bad("a rayleigh child is supported with depolarization = 0 only");
+    }
+    const bool has_grid = b->grid_res[0] || b->grid_res[1] || b->grid_res[2];
+    uint64_t n_grid = 0;
+    if (has_grid) {
+        if (!b->grid_res[0] || !b->grid_res[1] || !b->grid_res[2]) return bad("a weight grid needs three non-zero resolutions");
+        if (!b->grid_data) return bad("NULL weight grid data");
+        if (grid_bricked_size(b->grid_res) >= (1ull << 32)) return bad("weight grid above 2^32 texels");
+        n_grid = (uint64_t)b->grid_res[0] * b->grid_res[1] * b->grid_res[2];
+        if (!all_finite(b->grid_data, n_grid) || !all_finite(b->grid_to_local, 12))
+            return bad("the weight grid and its transform must be finite");
+    } else if (!std::isfinite(b->weight)) {
+        return bad("the weight must be finite");
+    }
+    std::vector<DMedium> media = s->h_dmedia;
+    std::vector<std::vector<PhaseRec>> tabs = s->h_phase_tabs;
+    std::vector<mh_scene::BlendHost> blends = s->h_blends;
+    mh_scene::BlendHost &h = blends[medium];
+    for (int c = 0; c < 2; ++c) {
+        // a child that stays tabulated keeps its table (a second call: update() of a child's g or of the weight's form)
+        if (!h.set || h.rec.phase[c] != MH_PHASE_TABULATED || b->phase[c] != MH_PHASE_TABULATED) {
+            h.tab[c].clear();
+            h.rec.tab_valid[c] = 0;
+        }
+        h.rec.phase[c] = b->phase[c];
+        h.rec.g[c] = b->g[c];
+    }
+    h.set = true;
+    h.rec.weight = has_grid ? 0.f : b->weight;
+    h.rec.has_grid = has_grid ? 1u : 0u;
+    memset(h.rec.res, 0, sizeof(h.rec.res));
+    memset(h.rec.to_local, 0, sizeof(h.rec.to_local));
+    h.rec.grid_offset = h.rec.pad = 0;
+    h.grid.clear();
+    if (has_grid) {
+        memcpy(h.rec.res, b->grid_res, 12);
+        memcpy(h.rec.to_local, b->grid_to_local, sizeof(h.rec.to_local));
+        h.grid.resize(grid_bricked_size(b->grid_res));
+        grid_to_bricks(b->grid_data, b->grid_res, h.grid.data());
+    }
+    return commit_phase_data(s, fn, media, tabs, blends, true);
+}
+
+int mh_scene_update_phase_blend_weight(mh_scene *s, uint32_t medium, const float *data, uint64_t n) {
+    const char *fn = "mh_scene_update_phase_blend_weight: ";
+    auto bad = [&](const char *why) { return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + why); };
+    if (!s || !data) return bad("NULL argument");
+    if (medium >= s->n_media) return bad("medium index out of bounds");
+    if (s->h_dmedia[medium].phase != MH_PHASE_BLEND || !s->h_blends[medium].set)
+        return bad("the medium has no blend (mh_scene_set_phase_blend)");
+    mh_scene::BlendHost &h = s->h_blends[medium];
+    const uint64_t want = h.rec.has_grid ? (uint64_t)h.rec.res[0] * h.rec.res[1] * h.rec.res[2] : 1ull;
+    if (n != want) return bad("size mismatch (a weight grid's x * y * z values, or 1 for a constant weight)");
+    if (!all_finite(data, n)) return bad("the weight must be finite");
+    MH_HIP(hipSetDevice(s->device));
+    MH_HIP(hipStreamSynchronize(s->stream));  // earlier calls may still read the old weight
+    if (h.rec.has_grid) {
+        std::vector<float> bricked(h.grid.size());
+        grid_to_bricks(data, h.rec.res, bricked.data());
+        MH_HIP(hipMemcpyAsync(s->grid.as<float>() + h.rec.grid_offset, bricked.data(), bricked.size() * sizeof(float),
+                              hipMemcpyHostToDevice, s->stream));
+        MH_HIP(hipStreamSynchronize(s->stream));
+        h.grid = std::move(bricked);
+    } else {
+        DBlend rec = h.rec;
+        rec.weight = *data;
+        MH_HIP(hipMemcpyAsync(s->phase_tab.as<PhaseRec>() + s->h_dmedia[medium].tab_offset, &rec, sizeof(DBlend),
+                              hipMemcpyHostToDevice, s->stream));
+        MH_HIP(hipStreamSynchronize(s->stream));
+        h.rec = rec;
+    }
+    return MH_OK;
+}
+
+// a tabulated medium without its table, or a blend medium without its blend
+// (or without a tabulated child's table): the kernels would read null data
 static int check_phase_tables(const mh_scene *s, const char *fn) {
-    for (uint32_t m = 0; m < s->n_media; ++m)
+    for (uint32_t m = 0; m < s->n_media; ++m) {
         if (s->h_dmedia[m].phase == MH_PHASE_TABULATED && s->h_dmedia[m].tab_n == 0)
             return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + ": medium " + std::to_string(m) +
                                                           " has a tabulated phase function but no table "
                                                           "(call mh_scene_set_phase_table after mh_scene_create)");
+        if (s->h_dmedia[m].phase == MH_PHASE_BLEND && s->h_dmedia[m].tab_n == 0)
+            return set_error(MH_ERR_INVALID_ARGUMENT,
+                             std::string(fn) + ": medium " + std::to_string(m) +
+                                 (s->h_blends[m].set ? " has a blend phase function with a tabulated child but no table for it "
+                                                       "(call mh_scene_set_phase_blend_table after mh_scene_set_phase_blend)"
+                                                     : " has a blend phase function but no blend "
+                                                       "(call mh_scene_set_phase_blend after mh_scene_create)"));
+    }
     return MH_OK;
 }
 
-// Phase-function queries: a grid-stride kernel around phase_sample / phase_eval
-static int phase_query(mh_scene *s, const char *fn, bool sample, uint32_t medium, uint64_t n, const float *in,
-                       float *out, float *pdf, uint32_t flags) {
+// Phase-function queries: a grid-stride kernel around phase_sample / phase_eval.
+// at: the position-aware calls (sample: in = u1 u2x u2y, pos = the interaction points)
+static int phase_query(mh_scene *s, const char *fn, bool sample, bool at, uint32_t medium, uint64_t n, const float *in,
+                       const float *pos, float *out, float *pdf, uint32_t flags) {
     if (!s) return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + ": NULL scene");
     if (medium >= s->n_media) return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + ": medium index out of bounds");
-    if (n && (!in || !out || (sample && !pdf))) return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + ": NULL argument");
+    if (n && (!in || !out || (sample && !pdf) || (at && !pos)))
+        return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + ": NULL argument");
     if (n >= (1ull << 32)) return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + ": more than 2^32 - 1 items");
+    if (!at && s->h_dmedia[medium].phase == MH_PHASE_BLEND)
+        return set_error(MH_ERR_INVALID_ARGUMENT,
+                         std::string(fn) + ": a blend phase function needs sample1 and the interaction point "
+                                           "(call mh_phase_sample_at / mh_phase_eval_at)");
     if (int rc = check_phase_tables(s, fn)) return rc;
     if (n == 0) return MH_OK;
     MH_HIP(hipSetDevice(s->device));
     hipStream_t st = s->stream;
     const bool dev = flags & MH_FLAG_DEVICE_POINTERS;
-    const uint64_t n_in = sample ? 2 * n : 3 * n, n_out = sample ? 3 * n : n;
-    const float *d_in = in;
+    const uint64_t n_in = sample ? (at ? 3 * n : 2 * n) : 3 * n, n_out = sample ? 3 * n : n;
+    const float *d_in = in, *d_pos = at ? pos : nullptr;
     float *d_out = out, *d_pdf = pdf;
     if (!dev) {
         MH_HIP(s->tmp_a.alloc(n_in * 4));
         MH_HIP(hipMemcpyAsync(s->tmp_a.ptr, in, n_in * 4, hipMemcpyHostToDevice, st));
         d_in = s->tmp_a.as<float>();
+        if (at) {
+            MH_HIP(s->tmp_c.alloc(3 * n * 4));
+            MH_HIP(hipMemcpyAsync(s->tmp_c.ptr, pos, 3 * n * 4, hipMemcpyHostToDevice, st));
+            d_pos = s->tmp_c.as<float>();
+        }
         MH_HIP(s->tmp_b.alloc((n_out + n) * 4));
         d_out = s->tmp_b.as<float>();
         d_pdf = d_out + n_out;
     }
     const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)device_cus(s->device) * 8);
-    MH_HIP(launch_phase_query(s->S, sample, medium, n, d_in, d_out, d_pdf, grid, st));
+    MH_HIP(launch_phase_query(s->S, sample, medium, n, d_in, d_pos, d_out, d_pdf, grid, st));
     if (!dev) {
         MH_HIP(hipMemcpyAsync(out, d_out, n_out * 4, hipMemcpyDeviceToHost, st));
         if (sample) MH_HIP(hipMemcpyAsync(pdf, d_pdf, n * 4, hipMemcpyDeviceToHost, st));
@@ -816,10 +1028,18 @@ static int phase_query(mh_scene *s, const char *fn, bool sample, uint32_t medium
     return MH_OK;
 }
 int mh_phase_sample(mh_scene *s, uint32_t medium, uint64_t n, const float *u, float *wo, float *pdf, uint32_t flags) {
-    return phase_query(s, "mh_phase_sample", true, medium, n, u, wo, pdf, flags);
+    return phase_query(s, "mh_phase_sample", true, false, medium, n, u, nullptr, wo, pdf, flags);
 }
 int mh_phase_eval(mh_scene *s, uint32_t medium, uint64_t n, const float *wo, float *value, uint32_t flags) {
-    return phase_query(s, "mh_phase_eval", false, medium, n, wo, value, nullptr, flags);
+    return phase_query(s, "mh_phase_eval", false, false, medium, n, wo, nullptr, value, nullptr, flags);
+}
+int mh_phase_sample_at(mh_scene *s, uint32_t medium, uint64_t n, const float *u, const float *pos, float *wo, float *pdf,
+                       uint32_t flags) {
+    return phase_query(s, "mh_phase_sample_at", true, true, medium, n, u, pos, wo, pdf, flags);
+}
+int mh_phase_eval_at(mh_scene *s, uint32_t medium, uint64_t n, const float *wo, const float *pos, float *value,
+                     uint32_t flags) {
+    return phase_query(s, "mh_phase_eval_at", false, true, medium, n, wo, pos, value, nullptr, flags);
 }
 
 // ---------------------------------------------------------------------------

@@ -149,16 +149,41 @@ struct alignas(16) PhaseRec { float x, y, c_prev, c; };
 
 struct DMedium {
     uint32_t type, phase, flags;
-    uint32_t tab_offset;                  // tabulated phase: first record (the header) in DScene::phase_tab
+    uint32_t tab_offset;                  // tabulated phase: first record (the header) in DScene::phase_tab;
+                                          // blend: where its DBlend starts there
     float g, scale, maj, sigma_t_const;   // maj = scale * max(grid) (heterogeneous.cpp:163)
     float albedo[4];
     uint32_t res[4];
     uint64_t grid_offset;   // first float of the medium's bricked grid (grid_index)
-    uint32_t tab_n;         // tabulated phase: nodes (0: no table yet)
+    uint32_t tab_n;         // tabulated phase: nodes (0: no table yet); blend: 1 once it is attached
     uint32_t tab_valid;     // its first | last << 16 interval with positive mass (m_valid)
     float to_local[12];
     float bbox_min[4], bbox_max[4];
+    static constexpr bool kFarLookups = false;  // grid_setup: sigma_t is looked up inside the medium's box only
 };
+
+// A MH_PHASE_BLEND medium's phase function (BlendPhaseFunction,
+// src/phase/blendphase.cpp, two children; mh_scene_set_phase_blend): the
+// children as the fields of DMedium that phase_eval / phase_sample read, and
+// weight_0 -- a constant, or (has_grid) a one-channel grid of its own in
+// DScene::grid, read by grid_eval through res / grid_offset / to_local.  It
+// lies in DScene::phase_tab at DMedium::tab_offset, in the place of 8 records,
+// ahead of its tabulated children's tables: DScene keeps its size (the
+// kernels of scenes without a blend keep their registers), and k_vol_sched
+// stages it into LDS with the tables.
+struct alignas(16) DBlend {
+    uint32_t phase[2];
+    float g[2];
+    uint32_t tab_offset[2], tab_n[2], tab_valid[2];   // tabulated children: as DMedium's
+    float weight;
+    uint32_t has_grid;
+    uint32_t res[4];
+    uint64_t grid_offset, pad;
+    float to_local[12];
+    static constexpr bool kFarLookups = true;   // grid_setup: looked up outside its box (the medium's scatter points)
+};
+static_assert(sizeof(DBlend) == 8 * sizeof(PhaseRec), "a DBlend takes 8 records of DScene::phase_tab");
+constexpr uint32_t kBlendRecs = 8;
 
 // PRBVolpathIntegrator.prepare_scene (prbvolpath.py:76-89), from the media of the shapes
 constexpr uint32_t kVolHandleNull = 1u;       // some medium is heterogeneous
@@ -166,6 +191,8 @@ constexpr uint32_t kVolNeeHomogeneous = 2u;   // some medium is homogeneous
 // not prepare_scene's: some medium's phase function is rayleigh or tabulated
 // (launch_vol_sched: volpath's machine with those branches; else the one without)
 constexpr uint32_t kVolPhaseExt = 4u;
+// some medium's phase function is a blend: the kernels compiled with it (kPhBlend, mh_shading.hpp)
+constexpr uint32_t kVolPhaseBlend = 8u;
 
 struct DScene {                 // kernel argument (by value)
     const Node *nodes;
@@ -215,7 +242,7 @@ struct DScene {                 // kernel argument (by value)
     // as the device's division), so the bounce kernels hold no per-lane loop-invariant quotients
     float inv_width, inv_height, inv_n_emitters;
     float n_emitters_f, env_pdf;  // (float)n_emitters; kInv4Pi * inv_n_emitters (a constant emitter's pdf)
-    const PhaseRec *phase_tab;    // the tabulated phase functions' tables (DMedium::tab_offset; nullptr: none)
+    const PhaseRec *phase_tab;    // the tabulated phase functions' tables and the blends' records (DMedium::tab_offset; nullptr: none)
     uint32_t phase_tab_bytes;     // their size
     uint32_t phase_lds_bytes;     // per launch: phase_tab_bytes when k_vol_sched stages them into LDS, else 0
 };

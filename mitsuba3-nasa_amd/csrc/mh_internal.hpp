@@ -92,10 +92,12 @@ size_t lds_bytes(const DScene &S, uint32_t block);
 hipError_t launch_trace(const DScene &S, bool shadow, uint64_t n, const float *rays, float *t,
                         float *u, float *v, uint32_t *prim, uint32_t *shape, uint32_t *inst, uint32_t *occ,
                         uint32_t grid, hipStream_t st);
-// phase_sample (in = u1[n] u2[n] -> wo x[n] y[n] z[n], pdf[n]) or phase_eval
-// (in = wo x[n] y[n] z[n] -> value[n]) of one medium
+// phase_sample (in = u2x[n] u2y[n] -> wo x[n] y[n] z[n], pdf[n]) or phase_eval
+// (in = wo x[n] y[n] z[n] -> value[n]) of one medium; with pos = x[n] y[n] z[n]
+// (the interaction points: mh_phase_sample_at / mh_phase_eval_at) the sample's
+// in is u1[n] u2x[n] u2y[n]
 hipError_t launch_phase_query(const DScene &S, bool sample, uint32_t medium, uint64_t n, const float *in,
-                              float *wo_or_value, float *pdf, uint32_t grid, hipStream_t st);
+                              const float *pos, float *wo_or_value, float *pdf, uint32_t grid, hipStream_t st);
 hipError_t launch_render(const DScene &S, const IntegratorParams &in, const LaneMap &lm,
                          uint32_t seed_value, uint32_t n_passes, uint64_t n, uint64_t plane,
                          float *out, unsigned long long *counters, hipStream_t st, int alpha = 0);

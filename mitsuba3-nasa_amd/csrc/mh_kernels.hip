@@ -110,7 +110,8 @@ k_trace_shadow(DScene S, uint64_t n, const float *__restrict__ rays, uint32_t *_
 #ifndef MH_VOL_WAVES
 #define MH_VOL_WAVES 4  // volpath: 128 VGPRs (+ some scratch) measured +10 % over 2 waves (tools/exp_volwaves.sh)
 #endif
-template <int Kind, bool InLds>
+// Ph: the phase functions of the volumetric integrators (kPhBlend: scenes with a blend medium)
+template <int Kind, bool InLds, int Ph = kPhExt>
 __global__ void __launch_bounds__(256, (Kind == MH_INTEGRATOR_VOLPATH || Kind == MH_INTEGRATOR_PRBVOLPATH) ? MH_VOL_WAVES : 1)
 k_render(DScene S, IntegratorParams in, LaneMap lm, uint32_t seed_value, uint32_t n_passes,
          uint64_t n, uint64_t plane, float *__restrict__ out, unsigned long long *__restrict__ counters,
@@ -135,9 +136,9 @@ k_render(DScene S, IntegratorParams in, LaneMap lm, uint32_t seed_value, uint32_
                 L = prb_sample<false>(S, B, in, rng, r, v3(0, 0, 0), v3(0, 0, 0), nullptr, n_closest, n_shadow,
                                       &valid);
             else if (Kind == MH_INTEGRATOR_VOLPATH)
-                L = volpath_sample(S, B, in, rng, r, n_closest, n_shadow, &valid);
+                L = volpath_sample<Ph>(S, B, in, rng, r, n_closest, n_shadow, &valid);
             else if (Kind == MH_INTEGRATOR_PRBVOLPATH)
-                L = prbvol_sample<0>(S, B, in, rng, r, v3(0, 0, 0), v3(0, 0, 0), nullptr, n_closest, n_shadow,
+                L = prbvol_sample<0, Ph>(S, B, in, rng, r, v3(0, 0, 0), v3(0, 0, 0), nullptr, n_closest, n_shadow,
                                          &valid);
             else
                 L = path_sample(S, B, in, rng, r, n_closest, n_shadow, &valid);
@@ -718,7 +719,7 @@ __global__ void k_develop(uint64_t n_px, const float *__restrict__ film, float *
 // <adj, tangent> sum is then dL_c (the medium's sigma_t adjoint mixes the
 // channels, so one replay cannot give all three)
 // ---------------------------------------------------------------------------
-template <bool Vol, bool InLds>
+template <bool Vol, bool InLds, int Ph = kPhExt>
 __global__ void __launch_bounds__(256, Vol ? MH_VOL_WAVES : 1)
 k_render_forward(DScene S, IntegratorParams in, LaneMap lm, uint32_t seed_value, uint64_t n, uint64_t plane,
                  float *__restrict__ out, GradArgs ga, unsigned long long *__restrict__ counters, int alpha) {
@@ -740,14 +741,14 @@ k_render_forward(DScene S, IntegratorParams in, LaneMap lm, uint32_t seed_value,
         bool valid = false;
         if (Vol) {
             Pcg rng_primal = rng;  // sampler.clone()
-            const V3 Lp = prbvol_sample<0>(S, B, in, rng_primal, r, v3(0, 0, 0), v3(0, 0, 0), nullptr, n_closest,
-                                           n_shadow, &valid);
+            const V3 Lp = prbvol_sample<0, Ph>(S, B, in, rng_primal, r, v3(0, 0, 0), v3(0, 0, 0), nullptr, n_closest,
+                                               n_shadow, &valid);
             float d[3];
 #pragma unroll 1
             for (int c = 0; c < 3; ++c) {
                 Pcg rc = rng;
                 g.fsum = 0.f;
-                prbvol_sample<1>(S, B, in, rc, r, v3(c == 0 ? 1.f : 0.f, c == 1 ? 1.f : 0.f, c == 2 ? 1.f : 0.f), Lp,
+                prbvol_sample<1, Ph>(S, B, in, rc, r, v3(c == 0 ? 1.f : 0.f, c == 1 ? 1.f : 0.f, c == 2 ? 1.f : 0.f), Lp,
                                  &g, n_closest, n_shadow);
                 d[c] = g.fsum;
             }
@@ -842,7 +843,7 @@ struct PvpWork {
     uint32_t main_cap;
 };
 
-template <bool InLds>
+template <bool InLds, int Ph = kPhExt>
 __global__ void __launch_bounds__(256, MH_VOL_WAVES)
 k_prbvol_backward(DScene S, IntegratorParams in, LaneMap lm, uint32_t seed_value, uint64_t n, int coalesce,
                   const float *__restrict__ grad_in, GradArgs ga, unsigned long long *__restrict__ counters,
@@ -880,14 +881,14 @@ k_prbvol_backward(DScene S, IntegratorParams in, LaneMap lm, uint32_t seed_value
             Pcg rng_primal = rng;  // sampler.clone()
             if (wk.main) {  // single pass: primal + logged adjoint terms, replay only on overflow
                 MainLog ml{wk.main, nl.stride, wk.main_cap, nl.t, 0u, false};
-                const V3 Lp = prbvol_sample<2>(S, B, in, rng_primal, r, dL, v3(0, 0, 0), &g, n_closest, n_shadow,
-                                               nullptr, &nl, &ml);
+                const V3 Lp = prbvol_sample<2, Ph>(S, B, in, rng_primal, r, dL, v3(0, 0, 0), &g, n_closest, n_shadow,
+                                                   nullptr, &nl, &ml);
                 if (!ml.overflow) pvp_log_apply(S, ml, Lp, g);
-                else prbvol_sample<3>(S, B, in, rng, r, dL, Lp, &g, n_closest, n_shadow);
+                else prbvol_sample<3, Ph>(S, B, in, rng, r, dL, Lp, &g, n_closest, n_shadow);
             } else {
-                V3 Lp = prbvol_sample<0>(S, B, in, rng_primal, r, v3(0, 0, 0), v3(0, 0, 0), nullptr, n_closest,
-                                         n_shadow);
-                prbvol_sample<1>(S, B, in, rng, r, dL, Lp, &g, n_closest, n_shadow, nullptr, wk.log ? &nl : nullptr);
+                V3 Lp = prbvol_sample<0, Ph>(S, B, in, rng_primal, r, v3(0, 0, 0), v3(0, 0, 0), nullptr, n_closest,
+                                             n_shadow);
+                prbvol_sample<1, Ph>(S, B, in, rng, r, dL, Lp, &g, n_closest, n_shadow, nullptr, wk.log ? &nl : nullptr);
             }
         }
         if (!wk.log) break;
@@ -939,32 +940,50 @@ hipError_t launch_trace(const DScene &S, bool shadow, uint64_t n, const float *r
     return hipGetLastError();
 }
 
-// mh_phase_sample / mh_phase_eval: phase_sample / phase_eval of one medium, as
-// the volumetric integrators call them, one item per lane (SoA in and out)
+// mh_phase_sample(_at) / mh_phase_eval(_at): phase_sample / phase_eval of one
+// medium, as the volumetric integrators call them, one item per lane (SoA in
+// and out).  pos (x[n] y[n] z[n], the _at calls) is the interaction point, at
+// which a blend looks its weight up once per item; u1 is sample1.  Without
+// pos (the calls without _at, which the API refuses on a blend medium) u holds
+// u2x[n] u2y[n] only.
 __global__ void __launch_bounds__(256)
-k_phase_sample(DScene S, uint32_t medium, uint64_t n, const float *__restrict__ u, float *__restrict__ wo,
-               float *__restrict__ pdf) {
+k_phase_sample(DScene S, uint32_t medium, uint64_t n, const float *__restrict__ u, const float *__restrict__ pos,
+               float *__restrict__ wo, float *__restrict__ pdf) {
     const DMedium &m = S.media[medium];
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         float p;
-        const V3 w = phase_sample(S, m, u[i], u[n + i], p);
+        V3 w;
+        if (pos) {
+            const float bw = phase_blend_weight<kPhBlend>(S, m, v3(pos[i], pos[n + i], pos[2 * n + i]));
+            w = phase_sample<kPhBlend>(S, m, u[n + i], u[2 * n + i], p, u[i], bw);
+        } else {
+            w = phase_sample(S, m, u[i], u[n + i], p);
+        }
         wo[i] = w.x; wo[n + i] = w.y; wo[2 * n + i] = w.z;
         pdf[i] = p;
     }
 }
 __global__ void __launch_bounds__(256)
-k_phase_eval(DScene S, uint32_t medium, uint64_t n, const float *__restrict__ wo, float *__restrict__ value) {
+k_phase_eval(DScene S, uint32_t medium, uint64_t n, const float *__restrict__ wo, const float *__restrict__ pos,
+             float *__restrict__ value) {
     const DMedium &m = S.media[medium];
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-        value[i] = phase_eval(S, m, v3(wo[i], wo[n + i], wo[2 * n + i]));
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const V3 w = v3(wo[i], wo[n + i], wo[2 * n + i]);
+        if (pos) {
+            const float bw = phase_blend_weight<kPhBlend>(S, m, v3(pos[i], pos[n + i], pos[2 * n + i]));
+            value[i] = phase_eval<kPhBlend>(S, m, w, bw);
+        } else {
+            value[i] = phase_eval(S, m, w);
+        }
+    }
 }
 hipError_t launch_phase_query(const DScene &S, bool sample, uint32_t medium, uint64_t n, const float *in,
-                              float *wo_or_value, float *pdf, uint32_t grid, hipStream_t st) {
+                              const float *pos, float *wo_or_value, float *pdf, uint32_t grid, hipStream_t st) {
     if (n == 0 || grid == 0) return hipSuccess;
-    if (sample) hipLaunchKernelGGL(k_phase_sample, dim3(grid), dim3(256), 0, st, S, medium, n, in, wo_or_value, pdf);
-    else hipLaunchKernelGGL(k_phase_eval, dim3(grid), dim3(256), 0, st, S, medium, n, in, wo_or_value);
+    if (sample) hipLaunchKernelGGL(k_phase_sample, dim3(grid), dim3(256), 0, st, S, medium, n, in, pos, wo_or_value, pdf);
+    else hipLaunchKernelGGL(k_phase_eval, dim3(grid), dim3(256), 0, st, S, medium, n, in, pos, wo_or_value);
     return hipGetLastError();
 }
 
@@ -981,10 +1000,20 @@ hipError_t launch_render(const DScene &S, const IntegratorParams &in, const Lane
         if (lds) hipLaunchKernelGGL((k_render<K, true>), g, b, sh, st, S, in, lm, seed_value, n_passes, n, plane, out, counters, alpha); \
         else hipLaunchKernelGGL((k_render<K, false>), g, b, sh, st, S, in, lm, seed_value, n_passes, n, plane, out, counters, alpha);    \
     } while (0)
+    // a scene with a blend medium: the volumetric kernels compiled with blendphase
+#define MH_LAUNCH_RENDER_BLEND(K)                                                                             \
+    do {                                                                                                      \
+        if (lds) hipLaunchKernelGGL((k_render<K, true, kPhBlend>), g, b, sh, st, S, in, lm, seed_value, n_passes, n, plane, out, counters, alpha); \
+        else hipLaunchKernelGGL((k_render<K, false, kPhBlend>), g, b, sh, st, S, in, lm, seed_value, n_passes, n, plane, out, counters, alpha);    \
+    } while (0)
+    const bool blend = S.vol_flags & kVolPhaseBlend;
     if (in.type == MH_INTEGRATOR_PRB) MH_LAUNCH_RENDER(MH_INTEGRATOR_PRB);
+    else if (in.type == MH_INTEGRATOR_VOLPATH && blend) MH_LAUNCH_RENDER_BLEND(MH_INTEGRATOR_VOLPATH);
     else if (in.type == MH_INTEGRATOR_VOLPATH) MH_LAUNCH_RENDER(MH_INTEGRATOR_VOLPATH);
+    else if (in.type == MH_INTEGRATOR_PRBVOLPATH && blend) MH_LAUNCH_RENDER_BLEND(MH_INTEGRATOR_PRBVOLPATH);
     else if (in.type == MH_INTEGRATOR_PRBVOLPATH) MH_LAUNCH_RENDER(MH_INTEGRATOR_PRBVOLPATH);
     else MH_LAUNCH_RENDER(MH_INTEGRATOR_PATH);
+#undef MH_LAUNCH_RENDER_BLEND
 #undef MH_LAUNCH_RENDER
     return hipGetLastError();
 }
@@ -997,7 +1026,10 @@ hipError_t launch_render_forward(const DScene &S, const IntegratorParams &in, co
     const size_t sh = lds_bytes(S, bs);
     const bool lds = S.lds_bytes_bvh != 0, vol = in.type == MH_INTEGRATOR_PRBVOLPATH;
     const dim3 g(blocks_for(n, bs)), b(bs);
-    if (vol && lds) hipLaunchKernelGGL((k_render_forward<true, true>), g, b, sh, st, S, in, lm, seed_value, n, plane, out, ga, counters, alpha);
+    const bool blend = vol && (S.vol_flags & kVolPhaseBlend);
+    if (blend && lds) hipLaunchKernelGGL((k_render_forward<true, true, kPhBlend>), g, b, sh, st, S, in, lm, seed_value, n, plane, out, ga, counters, alpha);
+    else if (blend) hipLaunchKernelGGL((k_render_forward<true, false, kPhBlend>), g, b, sh, st, S, in, lm, seed_value, n, plane, out, ga, counters, alpha);
+    else if (vol && lds) hipLaunchKernelGGL((k_render_forward<true, true>), g, b, sh, st, S, in, lm, seed_value, n, plane, out, ga, counters, alpha);
     else if (vol) hipLaunchKernelGGL((k_render_forward<true, false>), g, b, sh, st, S, in, lm, seed_value, n, plane, out, ga, counters, alpha);
     else if (lds) hipLaunchKernelGGL((k_render_forward<false, true>), g, b, sh, st, S, in, lm, seed_value, n, plane, out, ga, counters, alpha);
     else hipLaunchKernelGGL((k_render_forward<false, false>), g, b, sh, st, S, in, lm, seed_value, n, plane, out, ga, counters, alpha);
@@ -1321,7 +1353,12 @@ hipError_t launch_prb_backward(const DScene &S, const IntegratorParams &in, cons
             hipError_t e = hipMemsetAsync(head, 0, sizeof(unsigned long long), st);
             if (e != hipSuccess) return e;
         }
-        if (S.lds_bytes_bvh)
+        const bool blend = S.vol_flags & kVolPhaseBlend;
+        if (S.lds_bytes_bvh && blend)
+            hipLaunchKernelGGL((k_prbvol_backward<true, kPhBlend>), g, b, sh, st, S, in, lm, seed_value, n, coalesce, grad_in, ga, counters, wk);
+        else if (blend)
+            hipLaunchKernelGGL((k_prbvol_backward<false, kPhBlend>), g, b, sh, st, S, in, lm, seed_value, n, coalesce, grad_in, ga, counters, wk);
+        else if (S.lds_bytes_bvh)
             hipLaunchKernelGGL((k_prbvol_backward<true>), g, b, sh, st, S, in, lm, seed_value, n, coalesce, grad_in, ga, counters, wk);
         else
             hipLaunchKernelGGL((k_prbvol_backward<false>), g, b, sh, st, S, in, lm, seed_value, n, coalesce, grad_in, ga, counters, wk);

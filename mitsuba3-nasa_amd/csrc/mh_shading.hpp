@@ -2644,11 +2644,20 @@ struct GridLookup {
     float w0x, w0y, w0z, w1x, w1y, w1z;
     uint32_t o[8];  // tap (bx, by, bz) at o[bx | by << 1 | bz << 2] in the bricked grid
 };
-MH_DEV void grid_setup(const DMedium &m, V3 p, GridLookup &L) {
+// G: DMedium (sigma_t) or DBlend (a blend's weight_0): to_local, res, grid_offset
+template <class G>
+MH_DEV void grid_setup(const G &m, V3 p, GridLookup &L) {
     V3 q = xf_point(m.to_local, p);
     const int32_t rx = (int32_t)m.res[0], ry = (int32_t)m.res[1], rz = (int32_t)m.res[2];
     float px = __builtin_fmaf(q.x, (float)rx, -0.5f), py = __builtin_fmaf(q.y, (float)ry, -0.5f),
           pz = __builtin_fmaf(q.z, (float)rz, -0.5f);
+    if (G::kFarLookups) {
+        // a weight grid is looked up wherever its medium scatters, however far outside its own box: beyond
+        // [-1, r] both taps are the edge texel, and the clamp keeps floorf's conversion and ix + 1 in range
+        px = fminf(fmaxf(px, -1.f), (float)rx);
+        py = fminf(fmaxf(py, -1.f), (float)ry);
+        pz = fminf(fmaxf(pz, -1.f), (float)rz);
+    }
     int32_t ix = (int32_t)floorf(px), iy = (int32_t)floorf(py), iz = (int32_t)floorf(pz);
     L.w1x = px - (float)ix; L.w1y = py - (float)iy; L.w1z = pz - (float)iz;
     L.w0x = 1.f - L.w1x; L.w0y = 1.f - L.w1y; L.w0z = 1.f - L.w1z;
@@ -2671,7 +2680,8 @@ MH_DEV float grid_interp(const GridLookup &L, const float (&v)[8]) {
     float f0 = __builtin_fmaf(L.w0y, f00, L.w1y * f10), f1 = __builtin_fmaf(L.w0y, f01, L.w1y * f11);
     return __builtin_fmaf(L.w0z, f0, L.w1z * f1);
 }
-MH_DEV float grid_eval(const DScene &S, const DMedium &m, V3 p) {
+template <class G>
+MH_DEV float grid_eval(const DScene &S, const G &m, V3 p) {
     GridLookup L;
     grid_setup(m, p, L);
     const float *g = S.grid + m.grid_offset;
@@ -2802,20 +2812,73 @@ MH_DEV float eval_rayleigh(float cos_theta) { return ((3.f / 16.f) * kInvPi) * (
 
 // wo is local to Frame3f(ray.d) with wi = (0, 0, -1): the fork's tabphase and
 // rayleigh take the physics cosine (+1 = forward), which is wo.z there.
-// Ext = false leaves the two out: config 4 (HG) measured 1.2 % slower on
-// k_vol_sched<VolMachine> with them in its instruction stream
-// (profiles/phase_bench.txt), so a scene without such a medium runs that
-// machine without them (kVolPhaseExt).
-template <bool Ext = true>
-MH_DEV float phase_eval(const DScene &S, const DMedium &m, V3 wo) {
+// Ph: the phase functions compiled into the caller.  kPhHg leaves rayleigh and
+// tabphase out: config 4 (HG) measured 1.2 % slower on k_vol_sched<VolMachine>
+// with them in its instruction stream (profiles/phase_bench.txt), so a scene
+// without such a medium runs that machine without them (kVolPhaseExt).
+// kPhBlend adds blendphase (kVolPhaseBlend): a scene without a blend medium
+// runs kernels without its code (profiles/blend_kres.txt).
+constexpr int kPhHg = 0, kPhExt = 1, kPhBlend = 2;
+// a blend's child as the fields of DMedium that phase_eval / phase_sample read
+struct BlendChild {
+    uint32_t phase;
+    float g;
+    uint32_t tab_offset, tab_n, tab_valid;
+};
+MH_DEV const DBlend &blend_of(const DScene &S, const DMedium &m) {
+    return *reinterpret_cast<const DBlend *>(S.phase_tab + m.tab_offset);
+}
+MH_DEV BlendChild blend_child(const DBlend &b, int i) {
+    return BlendChild{b.phase[i], b.g[i], b.tab_offset[i], b.tab_n[i], b.tab_valid[i]};
+}
+// BlendPhaseFunction::eval_weight (blendphase.cpp:196-200) of child 0 at the
+// interaction point p: weight_0's eval_1 (a constant, or its grid: grid.cpp,
+// trilinear, clamp) clamped to [0, 1].  One lookup per real scatter event: the
+// callers keep the value for the event's phase_eval and phase_sample.  0 for
+// a medium without a blend.
+template <int Ph>
+MH_DEV float phase_blend_weight(const DScene &S, const DMedium &m, V3 p) {
+    if (Ph < kPhBlend || m.phase != MH_PHASE_BLEND) return 0.f;
+    const DBlend &b = blend_of(S, m);
+    const float w = b.has_grid ? grid_eval(S, b, p) : b.weight;
+    return fminf(fmaxf(w, 0.f), 1.f);
+}
+
+// M: DMedium, or a blend's BlendChild.  bw: phase_blend_weight of the
+// interaction (read for a blend medium only).  The blend sits in an
+// `if constexpr` that the kPhHg / kPhExt instances discard: their code is then
+// the functions' as they were before the blend, and k_vol_sched's instances of
+// scenes without a blend stay the kernels they were (profiles/blend_kres.txt).
+template <int Ph = kPhExt, class M = DMedium>
+MH_DEV float phase_eval(const DScene &S, const M &m, V3 wo, float bw = 0.f) {
+    if constexpr (Ph >= kPhBlend) {
+        if (m.phase == MH_PHASE_BLEND) {   // blendphase.cpp:246-251, weights w and 1.f - w (:219)
+            const DBlend &b = blend_of(S, m);
+            const float e0 = phase_eval<kPhExt>(S, blend_child(b, 0), wo), e1 = phase_eval<kPhExt>(S, blend_child(b, 1), wo);
+            return e0 * bw + e1 * (1.f - bw);
+        }
+    }
     if (m.phase == MH_PHASE_HG) return eval_hg(m.g, dot(wo, v3(0.f, 0.f, -1.f)));
-    if (!Ext) return kInv4Pi;
+    if (Ph == kPhHg) return kInv4Pi;
     if (m.phase == MH_PHASE_TABULATED) return tab_eval_pdf(S.phase_tab + m.tab_offset, m.tab_n, wo.z) * kInvTwoPi;
     if (m.phase == MH_PHASE_RAYLEIGH) return eval_rayleigh(wo.z);
     return kInv4Pi;
 }
-template <bool Ext = true>
-MH_DEV V3 phase_sample(const DScene &S, const DMedium &m, float s2x, float s2y, float &pdf) {
+// s1: PhaseFunction::sample's sample1, which only a blend reads
+template <int Ph = kPhExt, class M = DMedium>
+MH_DEV V3 phase_sample(const DScene &S, const M &m, float s2x, float s2y, float &pdf, float s1 = 0.f, float bw = 0.f) {
+    if constexpr (Ph >= kPhBlend) {
+        if (m.phase == MH_PHASE_BLEND) {
+            // blendphase.cpp:176-188 with cdf = {w, 1}: strict inequalities, so
+            // sample1 == 0 and sample1 == w select no child (wo = 0, pdf = 0: the
+            // path ends); the result is the child's, pdf included, not the
+            // mixture's.  The children do not read the rescaled sample1 (:180).
+            const bool c0 = s1 > 0.f && s1 < bw, c1 = s1 > bw && s1 < 1.f;
+            pdf = 0.f;
+            if (!c0 && !c1) return v3(0.f, 0.f, 0.f);
+            return phase_sample<kPhExt>(S, blend_child(blend_of(S, m), c0 ? 0 : 1), s2x, s2y, pdf);
+        }
+    }
     if (m.phase == MH_PHASE_HG) {
         const float g = m.g;
         float sqr_term = (1.f - g * g) / ((1.f - g) + (2.f * g) * s2x);
@@ -2827,7 +2890,7 @@ MH_DEV V3 phase_sample(const DScene &S, const DMedium &m, float s2x, float s2y, 
         pdf = eval_hg(g, -cos_theta);
         return v3(sin_theta * cp, sin_theta * sp, cos_theta);
     }
-    if (Ext && (m.phase == MH_PHASE_TABULATED || m.phase == MH_PHASE_RAYLEIGH)) {
+    if (Ph != kPhHg && (m.phase == MH_PHASE_TABULATED || m.phase == MH_PHASE_RAYLEIGH)) {
         float cos_theta;
         if (m.phase == MH_PHASE_TABULATED) {   // tabphase.cpp:99-119 (wo is not negated: the "[Kate]" note)
             cos_theta = tab_sample(S.phase_tab + m.tab_offset, m.tab_valid, s2x);
@@ -2839,7 +2902,7 @@ MH_DEV V3 phase_sample(const DScene &S, const DMedium &m, float s2x, float s2y, 
         float sp, cp;
         sincos_cephes((2.f * kPi) * s2y, sp, cp);
         const V3 wo = v3(sin_theta * cp, sin_theta * sp, cos_theta);
-        pdf = phase_eval(S, m, wo);
+        pdf = phase_eval<kPhExt>(S, m, wo);
         return wo;
     }
     pdf = kInv4Pi;
@@ -2996,6 +3059,8 @@ struct VolState {
     float pend_w;       // medium: MIS weight applied after the emitted radiance
     DirS ds;
     NeeState ns;
+    // (last: the kernels of scenes without a blend never touch it and keep their code)
+    float blend_w;      // medium scatter in a blend medium: phase_blend_weight (kPhBlend kernels only)
 };
 
 MH_DEV void volpath_init(const DScene &S, const IntegratorParams &in, Pcg &rng, RayT ray, VolState &v) {
@@ -3017,7 +3082,7 @@ MH_DEV void volpath_init(const DScene &S, const IntegratorParams &in, Pcg &rng, 
 }
 
 // pre: false when the path ends at the loop head
-template <bool Pk = false>
+template <bool Pk = false, int Ph = kPhExt>
 MH_DEV bool volpath_pre(const DScene &S, const LdsBvh &B, const IntegratorParams &in, Pcg &rng, VolState &v,
                         uint32_t &n_closest) {
     RayT &ray = v.ray;
@@ -3075,9 +3140,10 @@ MH_DEV bool volpath_pre(const DScene &S, const LdsBvh &B, const IntegratorParams
         const bool sample_emitters = !(m.flags & MH_MEDIUM_NO_EMITTER_SAMPLING);
         specular_chain = !sample_emitters;
         v.valid = true;  // valid_ray |= act_medium_scatter (volpath.cpp:223)
+        if (Ph >= kPhBlend) v.blend_w = phase_blend_weight<Ph>(S, m, mei.p);
         if (sample_emitters) {
             walk = nee_begin(S, mei.p, v3(0, 0, 0), nullptr, rng, medium, v.ds, v.ns);
-            const float ph = phase_eval(S, m, mei_to_local(mei, v.ds.d));
+            const float ph = phase_eval<Ph>(S, m, mei_to_local(mei, v.ds.d), Ph >= kPhBlend ? v.blend_w : 0.f);
             v.pend = throughput * ph;
             v.pend_w = mis_weight(v.ds.pdf, v.ds.delta ? 0.f : ph);
             v.nee_kind = kNeeMedium;
@@ -3128,7 +3194,7 @@ MH_DEV bool volpath_pre(const DScene &S, const LdsBvh &B, const IntegratorParams
 
 // post: the emitter sample's contribution, then phase / BSDF sampling; false
 // when the path has ended
-template <bool Ext = true>
+template <int Ph = kPhExt>
 MH_DEV bool volpath_post(const DScene &S, const IntegratorParams &in, Pcg &rng, VolState &v) {
     V3 &throughput = v.throughput, &result = v.result;
     if (v.nee_kind == kNeeMedium) result = result + (v.pend * nee_result(v.ns)) * v.pend_w;
@@ -3137,10 +3203,10 @@ MH_DEV bool volpath_post(const DScene &S, const IntegratorParams &in, Pcg &rng, 
     const MEI &mei = v.mei;
     if (act_scatter) {
         const DMedium &m = S.media[v.medium];
-        (void)rng.next_float();
+        const float s1 = rng.next_float();   // sample1: a blend's child selection
         const float s2x = rng.next_float(), s2y = rng.next_float();
         float ph_pdf;
-        V3 wo = phase_sample<Ext>(S, m, s2x, s2y, ph_pdf);
+        V3 wo = phase_sample<Ph>(S, m, s2x, s2y, ph_pdf, s1, Ph >= kPhBlend ? v.blend_w : 0.f);
         act_scatter = act_scatter && ph_pdf > 0.f;
         if (act_scatter) {
             v.ray = spawn_ray(mei.p, v3(0, 0, 0), mei_to_world(mei, wo));
@@ -3188,7 +3254,7 @@ MH_DEV bool volpath_post(const DScene &S, const IntegratorParams &in, Pcg &rng, 
 #ifndef MH_VOL_MAIN_PCT
 #define MH_VOL_MAIN_PCT 75  // measured best of 25..100 on config 4 (tools/bench_volpath.py)
 #endif
-template <bool Pk = false>
+template <bool Pk = false, int Ph = kPhExt>
 MH_DEV bool volpath_advance(const DScene &S, const LdsBvh &B, const IntegratorParams &in, Pcg &rng, VolState &v,
                             uint32_t &n_closest, uint32_t &n_shadow) {
     const bool walking = v.mode == kVolNee;
@@ -3198,17 +3264,18 @@ MH_DEV bool volpath_advance(const DScene &S, const LdsBvh &B, const IntegratorPa
         return true;
     }
     if (n_main * 100u < n_all * (uint32_t)MH_VOL_MAIN_PCT) return true;
-    if (v.mode == kVolPost && !volpath_post(S, in, rng, v)) return false;
-    if (!volpath_pre<Pk>(S, B, in, rng, v, n_closest)) return false;
-    if (v.mode == kVolPost) return volpath_post(S, in, rng, v);
+    if (v.mode == kVolPost && !volpath_post<Ph>(S, in, rng, v)) return false;
+    if (!volpath_pre<Pk, Ph>(S, B, in, rng, v, n_closest)) return false;
+    if (v.mode == kVolPost) return volpath_post<Ph>(S, in, rng, v);
     return true;
 }
 
+template <int Ph = kPhExt>
 MH_DEV V3 volpath_sample(const DScene &S, const LdsBvh &B, const IntegratorParams &in, Pcg &rng,
                          RayT ray, uint32_t &n_closest, uint32_t &n_shadow, bool *valid_out = nullptr) {
     VolState v;
     volpath_init(S, in, rng, ray, v);
-    while (volpath_advance(S, B, in, rng, v, n_closest, n_shadow)) {
+    while (volpath_advance<false, Ph>(S, B, in, rng, v, n_closest, n_shadow)) {
     }
     if (valid_out) *valid_out = v.valid;
     return v.result;
@@ -3551,7 +3618,7 @@ MH_DEV void charge_walk_log(const DScene &S, const float4 *e, uint32_t stride, u
 // Mode 0: primal; 1: adjoint replay (L = primal radiance); 2: primal + MainLog
 // + NEE gradients (single pass); 3: adjoint replay without the NEE gradients
 // (the fallback of a Mode-2 path whose log overflowed)
-template <int Mode>
+template <int Mode, int Ph = kPhExt>
 MH_DEV V3 prbvol_sample(const DScene &S, const LdsBvh &B, const IntegratorParams &in, Pcg &rng, RayT ray,
                         V3 dL, V3 L, GradCtx *g, uint32_t &n_closest, uint32_t &n_shadow,
                         bool *valid_out = nullptr, NeeLog *nl = nullptr, MainLog *ml = nullptr) {
@@ -3672,6 +3739,10 @@ MH_DEV V3 prbvol_sample(const DScene &S, const LdsBvh &B, const IntegratorParams
         V3 rho = v3(0.f, 0.f, 0.f);
         if (smooth) rho = tex_eval(S, S.bsdf_tex[b], si.uvx, si.uvy);
 
+        // a blend's weight_0 at the scatter event, for its NEE evaluation and its sample
+        float blend_w = 0.f;
+        if (Ph >= kPhBlend && act_scatter) blend_w = phase_blend_weight<Ph>(S, S.media[med], mei.p);
+
         // ---- emitter sampling (:242-270)
         const bool active_e_surface = active_surface && smooth && depth + 1 < in.max_depth;
         const bool sample_emitters = med != MH_INVALID && !(S.media[med].flags & MH_MEDIUM_NO_EMITTER_SAMPLING);
@@ -3696,7 +3767,7 @@ MH_DEV V3 prbvol_sample(const DScene &S, const LdsBvh &B, const IntegratorParams
                 nee_w = bv;
                 nee_pdf = bp;
             } else {
-                const float ph = phase_eval(S, S.media[med], mei_to_local(mei, ds.d));
+                const float ph = phase_eval<Ph>(S, S.media[med], mei_to_local(mei, ds.d), blend_w);
                 nee_w = v3(ph, ph, ph);
                 nee_pdf = ph;
             }
@@ -3732,10 +3803,10 @@ MH_DEV V3 prbvol_sample(const DScene &S, const LdsBvh &B, const IntegratorParams
         // ---- phase function sampling (:274-294)
         valid_ray = valid_ray || act_scatter;
         if (act_scatter) {
-            (void)rng.next_float();
+            const float s1 = rng.next_float();   // sample1: a blend's child selection
             const float s2x = rng.next_float(), s2y = rng.next_float();
             float ph_pdf;
-            const V3 wo = phase_sample(S, S.media[med], s2x, s2y, ph_pdf);
+            const V3 wo = phase_sample<Ph>(S, S.media[med], s2x, s2y, ph_pdf, s1, blend_w);
             act_scatter = act_scatter && ph_pdf > 0.f;
             if (act_scatter) {
                 ray = spawn_ray(mei.p, v3(0.f, 0.f, 0.f), mei_to_world(mei, wo));

@@ -36,7 +36,7 @@
 //   path record    C0 d.xyz last_pdf      C1 throughput.xyz pid
 //                  C2 result.xyz bits     C3 last_p.xyz pend_w
 //                  C4 pend.xyz pcg_v1     C5 mei.p.xyz depth
-//   surface NEE    X0 si.p.xyz wi.z       X1 si.n.xyz shape
+//   surface NEE    X0 si.p.xyz wi.z       X1 si.n.xyz shape      (medium NEE in a blend medium: X0.x = its weight)
 //                  X2 si.s.xyz rho.x      X3 si.t.xyz rho.y    X4 si.sn.xyz rho.z
 //   walk item      W0 o.xyz max_dist      W1 d.xyz medium
 //                  W2 emitter_val.xyz ds.dist  (walk result: nee.xyz)
@@ -100,6 +100,8 @@ MH_DEV float4 f4u(V3 a, uint32_t w) { return make_float4(a.x, a.y, a.z, __uint_a
 MH_DEV V3 xyz(const float4 &a) { return v3(a.x, a.y, a.z); }
 
 // ---- the state a suspended path carries through HBM ------------------------
+// (a medium scatter in a blend medium: its weight in X0.x, which only a surface uses otherwise)
+template <int Ph = kPhExt>
 MH_DEV void vw_store_path(const VwPlanes &P, uint64_t i, const VolState &v, uint32_t pid, uint32_t v1) {
     const uint32_t med = v.medium == MH_INVALID ? 0xffu : v.medium;
     const uint32_t bits = med | (v.nee_kind << 8) | (v.act_scatter ? kBitActScatter : 0u) |
@@ -120,6 +122,8 @@ MH_DEV void vw_store_path(const VwPlanes &P, uint64_t i, const VolState &v, uint
         P.at(kX2, i) = f4(v.si.s, v.rho.x);
         P.at(kX3, i) = f4(v.si.t_, v.rho.y);
         P.at(kX4, i) = f4(v.si.sn, v.rho.z);
+    } else if (Ph >= kPhBlend && v.act_scatter) {
+        P.at(kX0, i) = make_float4(v.blend_w, 0.f, 0.f, 0.f);
     }
 }
 
@@ -133,6 +137,7 @@ MH_DEV void vw_store_walk(const VwPlanes &P, uint64_t i, const VolState &v, cons
 }
 
 // resume a suspended path in kVolPost mode with its walk's result
+template <int Ph = kPhExt>
 MH_DEV void vw_load_path(const DScene &S, const VwPlanes &P, uint64_t i, VolState &v, Pcg &rng, uint32_t &pid,
                          uint32_t &v1) {
     const float4 c0 = P.at(kC0, i), c1 = P.at(kC1, i), c2 = P.at(kC2, i), c3 = P.at(kC3, i), c4 = P.at(kC4, i),
@@ -179,6 +184,7 @@ MH_DEV void vw_load_path(const DScene &S, const VwPlanes &P, uint64_t i, VolStat
         v.si.sn = xyz(x4);
         v.rho = v3(x2.w, x3.w, x4.w);
     }
+    if (Ph >= kPhBlend && !v.active_surface && v.act_scatter) v.blend_w = P.at(kX0, i).x;  // vw_store_path
     v.mode = kVolPost;
 }
 
@@ -206,7 +212,7 @@ MH_DEV void vw_range(const VwSeg &it, uint32_t n, uint32_t &r0, uint32_t &r1) {
 #ifndef MH_VW_MAIN_WAVES
 #define MH_VW_MAIN_WAVES 2
 #endif
-template <bool Fresh, bool InLds, bool Pk>
+template <bool Fresh, bool InLds, bool Pk, int Ph = kPhExt>
 __global__ void __launch_bounds__(256, MH_VW_MAIN_WAVES)
 k_vw_main(DScene S, IntegratorParams in, LaneMap lm, uint32_t seed_value, uint64_t n, uint64_t plane,
           float *__restrict__ out, VwPlanes cur, VwPlanes nxt, uint32_t seg_cap, const uint32_t *__restrict__ ctr_in,
@@ -252,7 +258,7 @@ k_vw_main(DScene S, IntegratorParams in, LaneMap lm, uint32_t seed_value, uint64
             out[4 * plane + pid] = sy;
             volpath_init(S, in, rng, r, v);
         } else {
-            vw_load_path(S, cur, base + item, v, rng, pid, v1);
+            vw_load_path<Ph>(S, cur, base + item, v, rng, pid, v1);
         }
     };
     uint32_t fetched = r0 + 64u;  // wave-uniform
@@ -268,14 +274,14 @@ k_vw_main(DScene S, IntegratorParams in, LaneMap lm, uint32_t seed_value, uint64
 #ifdef MH_EXP_VWCNT
             ++n_trips;
 #endif
-            if (v.mode == kVolPost) alive = volpath_post(S, in, rng, v);
-            if (alive) alive = volpath_pre<Pk>(S, B, in, rng, v, n_closest);
+            if (v.mode == kVolPost) alive = volpath_post<Ph>(S, in, rng, v);
+            if (alive) alive = volpath_pre<Pk, Ph>(S, B, in, rng, v, n_closest);
             if (!alive) ended = true;
             else susp = v.mode == kVolNee;
         }
         const uint32_t pos = vw_append(ctr_next, susp);
         if (susp) {
-            vw_store_path(nxt, base + pos, v, pid, v1);
+            vw_store_path<Ph>(nxt, base + pos, v, pid, v1);
             vw_store_walk(nxt, base + pos, v, rng, v1);
         }
         if (ended) vw_write_sample(out, plane, pid, v, alpha);
@@ -302,7 +308,7 @@ k_vw_main(DScene S, IntegratorParams in, LaneMap lm, uint32_t seed_value, uint64
 // suspended path and advances it through its remaining trips and walks
 // (volpath_advance, the megakernel's state machine), refilled per lane.
 // ---------------------------------------------------------------------------
-template <bool InLds, bool Pk>
+template <bool InLds, bool Pk, int Ph = kPhExt>
 __global__ void __launch_bounds__(256, MH_VW_MAIN_WAVES)
 k_vw_finish(DScene S, IntegratorParams in, uint64_t plane, float *__restrict__ out, VwPlanes cur, uint32_t seg_cap,
             const uint32_t *__restrict__ ctr_in, unsigned long long *__restrict__ counters, int alpha) {
@@ -324,10 +330,10 @@ k_vw_finish(DScene S, IntegratorParams in, uint64_t plane, float *__restrict__ o
     uint32_t pid = 0, v1 = 0;
     uint32_t fetched = r0 + 64u;
     bool has = r0 + vw_lane() < r1;
-    if (has) vw_load_path(S, cur, base + r0 + vw_lane(), v, rng, pid, v1);
+    if (has) vw_load_path<Ph>(S, cur, base + r0 + vw_lane(), v, rng, pid, v1);
     while (__builtin_amdgcn_ballot_w64(has) != 0) {
         bool ended = false;
-        if (has && !volpath_advance<Pk>(S, B, in, rng, v, n_closest, n_shadow)) {
+        if (has && !volpath_advance<Pk, Ph>(S, B, in, rng, v, n_closest, n_shadow)) {
             ended = true;
             vw_write_sample(out, plane, pid, v, alpha);
         }
@@ -336,7 +342,7 @@ k_vw_finish(DScene S, IntegratorParams in, uint64_t plane, float *__restrict__ o
         if (need) {
             const uint32_t cand = fetched + (uint32_t)__popcll(m & ((1ull << vw_lane()) - 1ull));
             has = cand < r1;
-            if (has) vw_load_path(S, cur, base + cand, v, rng, pid, v1);
+            if (has) vw_load_path<Ph>(S, cur, base + cand, v, rng, pid, v1);
         }
         fetched += (uint32_t)__popcll(m);
     }
@@ -470,13 +476,13 @@ struct WMei {
 };
 
 // end of a trip that needs no walk (volpath_pre's tail + volpath_post)
-template <bool Ext>
+template <int Ph>
 MH_DEV uint32_t vs_no_walk(const DScene &S, const IntegratorParams &in, Pcg &rng, VolState &v) {
     if (v.nee_kind != kNeeNone) {  // ds.pdf == 0: emitted = 0
         v.ns.transmittance = v3(0, 0, 0);
         v.ns.emitter_val = v3(0, 0, 0);
     }
-    return volpath_post<Ext>(S, in, rng, v) ? kPhHead : kPhFree;
+    return volpath_post<Ph>(S, in, rng, v) ? kPhHead : kPhFree;
 }
 
 // the medium block of volpath_pre after its (optional) intersection, up to
@@ -553,7 +559,7 @@ MH_DEV uint32_t vs_head(const DScene &S, const IntegratorParams &in, Pcg &rng, V
 }
 
 // SCATTER: a real medium interaction (volpath.cpp:224-252)
-template <bool Ext>
+template <int Ph>
 MH_DEV uint32_t vs_scatter(const DScene &S, const IntegratorParams &in, Pcg &rng, VolState &v) {
     mei_frame(v.mei);  // the merged medium step samples without it (identical values)
     const DMedium &m = S.media[v.medium];
@@ -565,20 +571,21 @@ MH_DEV uint32_t vs_scatter(const DScene &S, const IntegratorParams &in, Pcg &rng
     v.specular_chain = !sample_emitters;
     v.valid = true;  // valid_ray |= act_medium_scatter (volpath.cpp:223)
     bool walk = false;
+    if (Ph >= kPhBlend) v.blend_w = phase_blend_weight<Ph>(S, m, mei.p);  // once per scatter: NEE here, the sample in POST
     if (sample_emitters) {
         walk = nee_begin(S, mei.p, v3(0, 0, 0), nullptr, rng, v.medium, v.ds, v.ns);
-        const float ph = phase_eval<Ext>(S, m, mei_to_local(mei, v.ds.d));
+        const float ph = phase_eval<Ph>(S, m, mei_to_local(mei, v.ds.d), Ph >= kPhBlend ? v.blend_w : 0.f);
         v.pend = v.throughput * ph;
         v.pend_w = mis_weight(v.ds.pdf, v.ds.delta ? 0.f : ph);
         v.nee_kind = kNeeMedium;
     }
     v.active_surface = false;
     v.rho = v3(0, 0, 0);
-    return walk ? kPhWalk : vs_no_walk<Ext>(S, in, rng, v);
+    return walk ? kPhWalk : vs_no_walk<Ph>(S, in, rng, v);
 }
 
 // SURF: a surface interaction after its intersection (volpath.cpp:254-300)
-template <bool Ext>
+template <int Ph>
 MH_DEV uint32_t vs_surf(const DScene &S, const IntegratorParams &in, Pcg &rng, VolState &v) {
     const SI &si = v.si;
     const bool count_direct = v.depth == 0 || v.specular_chain;
@@ -607,7 +614,7 @@ MH_DEV uint32_t vs_surf(const DScene &S, const IntegratorParams &in, Pcg &rng, V
             v.nee_kind = kNeeSurface;
         }
     }
-    return walk ? kPhWalk : vs_no_walk<Ext>(S, in, rng, v);
+    return walk ? kPhWalk : vs_no_walk<Ph>(S, in, rng, v);
 }
 
 // ---- the walk (nee_step, volpath.cpp:361-448) cut at its intersection ------
@@ -1082,9 +1089,12 @@ MH_DEV uint32_t pv_medium_step(const DScene &S, const IntegratorParams &in, Pcg 
 
 // POST: the emitter sample's contribution (:256-270), phase sampling
 // (:274-294), BSDF sampling (:298-331) and the loop's tail test
-template <class V, class Hk>
+template <int Ph = kPhExt, class V, class Hk>
 MH_DEV uint32_t pv_post(const DScene &S, const LdsBvh &B, const IntegratorParams &in, Pcg &rng, V &v, Hk &hk,
                         uint32_t &n_shadow) {
+    // a blend's weight_0 at the scatter event, for its NEE evaluation and its sample
+    float blend_w = 0.f;
+    if (Ph >= kPhBlend && v.act_scatter) blend_w = phase_blend_weight<Ph>(S, S.media[v.med], v.mei.p);
     if (v.nee) {
         const V3 emitted = v.emitter_val * v.transmittance;
         V3 nee_w, bv = v3(0.f, 0.f, 0.f);
@@ -1095,7 +1105,7 @@ MH_DEV uint32_t pv_post(const DScene &S, const LdsBvh &B, const IntegratorParams
             nee_w = bv;
             nee_pdf = bp;
         } else {
-            const float ph = phase_eval(S, S.media[v.med], mei_to_local(v.mei, v.ds.d));
+            const float ph = phase_eval<Ph>(S, S.media[v.med], mei_to_local(v.mei, v.ds.d), blend_w);
             nee_w = v3(ph, ph, ph);
             nee_pdf = ph;
         }
@@ -1109,10 +1119,10 @@ MH_DEV uint32_t pv_post(const DScene &S, const LdsBvh &B, const IntegratorParams
     v.valid_ray = v.valid_ray || v.act_scatter;
     bool act_scatter = v.act_scatter;
     if (act_scatter) {
-        (void)rng.next_float();
+        const float s1 = rng.next_float();   // sample1: a blend's child selection
         const float s2x = rng.next_float(), s2y = rng.next_float();
         float ph_pdf;
-        const V3 wo = phase_sample(S, S.media[v.med], s2x, s2y, ph_pdf);
+        const V3 wo = phase_sample<Ph>(S, S.media[v.med], s2x, s2y, ph_pdf, s1, blend_w);
         act_scatter = act_scatter && ph_pdf > 0.f;
         if (act_scatter) {
             v.ray = spawn_ray(v.mei.p, v3(0.f, 0.f, 0.f), mei_to_world(v.mei, wo));
@@ -1214,13 +1224,14 @@ MH_DEV uint32_t pv_trace(const DScene &S, const LdsBvh &B, const IntegratorParam
 #ifndef MH_PVB_MERGE
 #define MH_PVB_MERGE 0
 #endif
-// Ext: with the rayleigh and tabulated phase functions' branches (phase_eval)
-template <bool Ext>
+// Ph: the phase functions compiled in (phase_eval: kPhHg, kPhExt with rayleigh
+// and tabphase, kPhBlend with blendphase as well)
+template <int Ph>
 struct VolMachineT {
     using State = VolState;
     // kMergeMed: HEAD and WALK lanes share a trip (vs_medium_step)
     static constexpr bool kPrb = false, kWritesPos = true, kDeferEnd = false, kMergeMed = MH_VS_MERGE != 0;
-    static constexpr bool kPhaseTab = Ext;  // k_vol_sched stages the phase tables (DScene::phase_lds_bytes)
+    static constexpr bool kPhaseTab = Ph != kPhHg;  // k_vol_sched stages the phase tables (DScene::phase_lds_bytes)
     MH_DEV VolMachineT(const VsBwdArgs &, const LaneMap &, uint32_t) {}
     MH_DEV void init(const DScene &S, const IntegratorParams &in, Pcg &rng, RayT r, State &v, float, float) {
         volpath_init(S, in, rng, r, v);
@@ -1234,10 +1245,10 @@ struct VolMachineT {
         return vs_trace<Pk>(S, B, in, rng, ph, v, wm, nc, ns);
     }
     MH_DEV uint32_t scatter(const DScene &S, const IntegratorParams &in, Pcg &rng, State &v) {
-        return vs_scatter<Ext>(S, in, rng, v);
+        return vs_scatter<Ph>(S, in, rng, v);
     }
     MH_DEV uint32_t surf(const DScene &S, const IntegratorParams &in, Pcg &rng, State &v) {
-        return vs_surf<Ext>(S, in, rng, v);
+        return vs_surf<Ph>(S, in, rng, v);
     }
     MH_DEV uint32_t walk(const DScene &S, Pcg &rng, State &v, WMei &wm) { return vs_walk(S, rng, v.ds, v.ns, wm); }
     MH_DEV uint32_t medium_step(const DScene &S, const IntegratorParams &in, Pcg &rng, State &v, WMei &wm, uint32_t ph,
@@ -1250,7 +1261,7 @@ struct VolMachineT {
         return vs_trace_hit(S, in, rng, ph, v, wm, h, r, nc, ns);
     }
     MH_DEV uint32_t post(const DScene &S, const LdsBvh &, const IntegratorParams &in, Pcg &rng, State &v, uint32_t &) {
-        return volpath_post<Ext>(S, in, rng, v) ? kPhHead : kPhFree;
+        return volpath_post<Ph>(S, in, rng, v) ? kPhHead : kPhFree;
     }
     MH_DEV void end(const DScene &, const LdsBvh &, const IntegratorParams &, float *out, uint64_t plane,
                     uint32_t pid, const State &v, int alpha, uint32_t &, uint32_t &) {
@@ -1258,8 +1269,9 @@ struct VolMachineT {
     }
     MH_DEV void finish() {}
 };
-using VolMachine = VolMachineT<true>;
-using VolMachineHg = VolMachineT<false>;   // scenes whose media are all isotropic or HG
+using VolMachine = VolMachineT<kPhExt>;
+using VolMachineHg = VolMachineT<kPhHg>;        // scenes whose media are all isotropic or HG
+using VolMachineBlend = VolMachineT<kPhBlend>;  // scenes with a blend medium (kVolPhaseBlend)
 
 struct PvMachine {
     using State = PvState;
@@ -1306,6 +1318,15 @@ struct PvMachine {
         if (alpha) out[5 * plane + pid] = v.valid_ray ? 1.f : 0.f;  // aovs[3] (integrator.cpp:1229-1231)
     }
     MH_DEV void finish() {}
+};
+// PvMachine for a scene with a blend medium: POST with blendphase compiled in,
+// so that k_vol_sched<PvMachine> stays the kernel of every other scene
+struct PvMachineBlend : PvMachine {
+    using PvMachine::PvMachine;
+    MH_DEV uint32_t post(const DScene &S, const LdsBvh &B, const IntegratorParams &in, Pcg &rng, State &v,
+                         uint32_t &ns) {
+        return pv_post<kPhBlend>(S, B, in, rng, v, h, ns);
+    }
 };
 
 // ===========================================================================
@@ -1913,8 +1934,9 @@ hipError_t launch_vol_sched(const DScene &S0, const IntegratorParams &in, const 
     if (n == 0) return hipSuccess;
     const bool pk = vol_packet(S0), tab = vs_tables(S0);
     DScene S;
-    hipError_t e = in.type == MH_INTEGRATOR_PRBVOLPATH ? vs_launch_scene<PvMachine>(S0, pk, tab, S)
-                                                       : vs_launch_scene<VolMachine>(S0, pk, tab, S);
+    const bool blend = S0.vol_flags & kVolPhaseBlend, pv = in.type == MH_INTEGRATOR_PRBVOLPATH;
+    hipError_t e = pv ? (blend ? vs_launch_scene<PvMachineBlend>(S0, pk, tab, S) : vs_launch_scene<PvMachine>(S0, pk, tab, S))
+                      : (blend ? vs_launch_scene<VolMachineBlend>(S0, pk, tab, S) : vs_launch_scene<VolMachine>(S0, pk, tab, S));
     if (e != hipSuccess) return e;
     const size_t sh = lds_bytes(S, 256);
     const bool lds = S.lds_bytes_bvh != 0;
@@ -1923,7 +1945,9 @@ hipError_t launch_vol_sched(const DScene &S0, const IntegratorParams &in, const 
                        in, lm, seed_value, n, plane, out, counters, work, alpha, VsBwdArgs{})
 #define MH_VS(L, P, T)                                                  \
     do {                                                                \
-        if (in.type == MH_INTEGRATOR_PRBVOLPATH) MH_VS1(PvMachine, L, P, T); \
+        if (pv && blend) MH_VS1(PvMachineBlend, L, P, T);               \
+        else if (pv) MH_VS1(PvMachine, L, P, T);                        \
+        else if (blend) MH_VS1(VolMachineBlend, L, P, T);               \
         else if (S.vol_flags & kVolPhaseExt) MH_VS1(VolMachine, L, P, T); \
         else MH_VS1(VolMachineHg, L, P, T);                             \
     } while (0)
@@ -1963,6 +1987,21 @@ struct PvBwdMachineEm : PvBwdMachine {
         return pv_post(S, B, in, rng, v, *this, ns);
     }
 };
+// both for a scene with a blend medium (as PvMachineBlend)
+struct PvBwdMachineBlend : PvBwdMachine {
+    using PvBwdMachine::PvBwdMachine;
+    MH_DEV uint32_t post(const DScene &S, const LdsBvh &B, const IntegratorParams &in, Pcg &rng, State &v,
+                         uint32_t &ns) {
+        return pv_post<kPhBlend>(S, B, in, rng, v, *this, ns);
+    }
+};
+struct PvBwdMachineEmBlend : PvBwdMachineEm {
+    using PvBwdMachineEm::PvBwdMachineEm;
+    MH_DEV uint32_t post(const DScene &S, const LdsBvh &B, const IntegratorParams &in, Pcg &rng, State &v,
+                         uint32_t &ns) {
+        return pv_post<kPhBlend>(S, B, in, rng, v, *this, ns);
+    }
+};
 
 #ifdef MH_EXP_VSCNT
 extern "C" int mh_exp_vs_sub(unsigned long long *out, int reset) {
@@ -1985,8 +2024,10 @@ hipError_t launch_vol_sched_bwd(const DScene &S0, const IntegratorParams &in, co
         return hipErrorInvalidValue;
     const bool pk = vol_packet(S0), tab = vs_tables(S0);
     DScene S;
-    hipError_t e = bw.ga.emitter_off ? vs_launch_scene<PvBwdMachineEm>(S0, pk, tab, S)
-                                     : vs_launch_scene<PvBwdMachine>(S0, pk, tab, S);
+    const bool blend = S0.vol_flags & kVolPhaseBlend;
+    hipError_t e = bw.ga.emitter_off
+                       ? (blend ? vs_launch_scene<PvBwdMachineEmBlend>(S0, pk, tab, S) : vs_launch_scene<PvBwdMachineEm>(S0, pk, tab, S))
+                       : (blend ? vs_launch_scene<PvBwdMachineBlend>(S0, pk, tab, S) : vs_launch_scene<PvBwdMachine>(S0, pk, tab, S));
     if (e != hipSuccess) return e;
     const size_t sh = lds_bytes(S, 256);
     const bool lds = S.lds_bytes_bvh != 0;
@@ -1998,7 +2039,9 @@ hipError_t launch_vol_sched_bwd(const DScene &S0, const IntegratorParams &in, co
                        st, S, in, lm, seed_value, n, (uint64_t)0, (float *)nullptr, counters, work, 0, bw)
 #define MH_VSB(L, P, T)                                                                                        \
     do {                                                                                                       \
-        if (bw.ga.emitter_off) MH_VSB1(PvBwdMachineEm, L, P, T);                                               \
+        if (bw.ga.emitter_off && blend) MH_VSB1(PvBwdMachineEmBlend, L, P, T);                                 \
+        else if (bw.ga.emitter_off) MH_VSB1(PvBwdMachineEm, L, P, T);                                          \
+        else if (blend) MH_VSB1(PvBwdMachineBlend, L, P, T);                                                   \
         else MH_VSB1(PvBwdMachine, L, P, T);                                                                   \
     } while (0)
     if (pk && tab) MH_VSB(false, true, true);
@@ -2013,7 +2056,7 @@ hipError_t launch_vol_sched_bwd(const DScene &S0, const IntegratorParams &in, co
 // A path whose MainLog overflowed: its adjoint replayed with L = its radiance
 // (prbvol_sample Mode 3, the NEE terms already charged), as k_prbvol_backward
 // does in place.
-template <bool InLds>
+template <bool InLds, int Ph = kPhExt>
 __global__ void __launch_bounds__(256)
 k_pvb_replay_paths(DScene S, IntegratorParams in, LaneMap lm, uint32_t seed_value, VsBwdArgs bw,
                    unsigned long long *counters) {
@@ -2031,7 +2074,7 @@ k_pvb_replay_paths(DScene S, IntegratorParams in, LaneMap lm, uint32_t seed_valu
         const float sx = (float)px + r.next_float(), sy = (float)py + r.next_float();
         const RayT ray = camera_ray(S, __builtin_fmaf(sx, S.inv_width, -0.f),
                                     __builtin_fmaf(sy, S.inv_height, -0.f));
-        prbvol_sample<3>(S, B, in, r, ray, v3(d.x, d.y, d.z), v3(e.x, e.y, e.z), &g, nc, ns);
+        prbvol_sample<3, Ph>(S, B, in, r, ray, v3(d.x, d.y, d.z), v3(e.x, e.y, e.z), &g, nc, ns);
     }
     flush_small_slots(g, bw.ga);
     if (counters) {
@@ -2081,11 +2124,14 @@ hipError_t launch_vol_sched_bwd_replays(const DScene &S, const IntegratorParams 
     // the lists' lengths stay on the device: every thread beyond them leaves at once
     const size_t sh = lds_bytes(S, 256);
     const uint32_t gp = (bw.ovf_cap + 255) / 256, gw = gp;
+    const bool blend = S.vol_flags & kVolPhaseBlend;  // the paths' replay samples phase functions; the walks' does not
     if (S.lds_bytes_bvh) {
-        hipLaunchKernelGGL(k_pvb_replay_paths<true>, dim3(gp), dim3(256), sh, st, S, in, lm, seed_value, bw, counters);
+        if (blend) hipLaunchKernelGGL((k_pvb_replay_paths<true, kPhBlend>), dim3(gp), dim3(256), sh, st, S, in, lm, seed_value, bw, counters);
+        else hipLaunchKernelGGL((k_pvb_replay_paths<true>), dim3(gp), dim3(256), sh, st, S, in, lm, seed_value, bw, counters);
         hipLaunchKernelGGL(k_pvb_replay_walks<true>, dim3(gw), dim3(256), sh, st, S, bw, counters);
     } else {
-        hipLaunchKernelGGL(k_pvb_replay_paths<false>, dim3(gp), dim3(256), sh, st, S, in, lm, seed_value, bw, counters);
+        if (blend) hipLaunchKernelGGL((k_pvb_replay_paths<false, kPhBlend>), dim3(gp), dim3(256), sh, st, S, in, lm, seed_value, bw, counters);
+        else hipLaunchKernelGGL((k_pvb_replay_paths<false>), dim3(gp), dim3(256), sh, st, S, in, lm, seed_value, bw, counters);
         hipLaunchKernelGGL(k_pvb_replay_walks<false>, dim3(gw), dim3(256), sh, st, S, bw, counters);
     }
     return hipGetLastError();
@@ -2110,6 +2156,7 @@ hipError_t launch_volwave(const DScene &S, const IntegratorParams &in, const Lan
     const size_t sh = lds_bytes(S, 256);
     const bool lds = S.lds_bytes_bvh != 0;
     const bool pk = vol_packet(S);
+    const bool blend = S.vol_flags & kVolPhaseBlend;  // the kernels compiled with blendphase
     // main / walk rounds while many paths are live, then one finish launch
     const uint32_t wave_rounds = (uint32_t)env::vw_rounds((int)kVwWaveRounds);
     for (uint32_t r = 0; r < rounds; ++r) {
@@ -2117,8 +2164,11 @@ hipError_t launch_volwave(const DScene &S, const IntegratorParams &in, const Lan
         const uint32_t *cin = ctr + (size_t)kVwCtr * r;
         uint32_t *cout = ctr + (size_t)kVwCtr * (r + 1);
         if (r == wave_rounds) {
-#define MH_VW_FIN(L, P) \
-    hipLaunchKernelGGL((k_vw_finish<L, P>), dim3(grid), dim3(256), sh, st, S, in, plane, out, c, seg_cap, cin, counters, alpha)
+#define MH_VW_FIN(L, P)                                                                                             \
+    do {                                                                                                            \
+        if (blend) hipLaunchKernelGGL((k_vw_finish<L, P, kPhBlend>), dim3(grid), dim3(256), sh, st, S, in, plane, out, c, seg_cap, cin, counters, alpha); \
+        else hipLaunchKernelGGL((k_vw_finish<L, P>), dim3(grid), dim3(256), sh, st, S, in, plane, out, c, seg_cap, cin, counters, alpha);                \
+    } while (0)
             if (pk) MH_VW_FIN(false, true);
             else if (lds) MH_VW_FIN(true, false);
             else MH_VW_FIN(false, false);
@@ -2126,17 +2176,23 @@ hipError_t launch_volwave(const DScene &S, const IntegratorParams &in, const Lan
             break;
         }
 #define MH_VW_MAIN(F, L, P)                                                                                   \
-    hipLaunchKernelGGL((k_vw_main<F, L, P>), dim3(grid), dim3(256), sh, st, S, in, lm, seed_value, n, plane, out, \
-                       c, x, seg_cap, cin, cout, counters, alpha)
+    do {                                                                                                      \
+        if (blend) hipLaunchKernelGGL((k_vw_main<F, L, P, kPhBlend>), dim3(grid), dim3(256), sh, st, S, in, lm, seed_value, n, plane, out, \
+                                      c, x, seg_cap, cin, cout, counters, alpha);                             \
+        else hipLaunchKernelGGL((k_vw_main<F, L, P>), dim3(grid), dim3(256), sh, st, S, in, lm, seed_value, n, plane, out, \
+                                c, x, seg_cap, cin, cout, counters, alpha);                                   \
+    } while (0)
 #define MH_VW_WALK(L, P) \
     hipLaunchKernelGGL((k_vw_walk<L, P>), dim3(grid), dim3(256), sh, st, S, x, seg_cap, cout, counters)
         if (pk) {
             if (r == 0) MH_VW_MAIN(true, false, true);
             else MH_VW_MAIN(false, false, true);
         } else if (r == 0) {
-            if (lds) MH_VW_MAIN(true, true, false); else MH_VW_MAIN(true, false, false);
+            if (lds) MH_VW_MAIN(true, true, false);
+            else MH_VW_MAIN(true, false, false);
         } else {
-            if (lds) MH_VW_MAIN(false, true, false); else MH_VW_MAIN(false, false, false);
+            if (lds) MH_VW_MAIN(false, true, false);
+            else MH_VW_MAIN(false, false, false);
         }
         if (r + 1 == rounds) break;  // depth < max_depth: no walk after the last round
         if (pk) MH_VW_WALK(false, true);

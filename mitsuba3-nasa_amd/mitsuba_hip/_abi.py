@@ -44,7 +44,7 @@ def image_channel_names(fmt: int):
     return {PIXEL_RGB: ["R", "G", "B"], PIXEL_Y: ["Y"], PIXEL_XYZ: ["X", "Y", "Z"],
             PIXEL_RGBA: ["R", "G", "B", "A"], PIXEL_YA: ["Y", "A"], PIXEL_XYZA: ["X", "Y", "Z", "A"]}[fmt]
 MEDIUM_HETEROGENEOUS, MEDIUM_HOMOGENEOUS = 0, 1
-PHASE_ISOTROPIC, PHASE_HG, PHASE_RAYLEIGH, PHASE_TABULATED = 0, 1, 2, 3
+PHASE_ISOTROPIC, PHASE_HG, PHASE_RAYLEIGH, PHASE_TABULATED, PHASE_BLEND = 0, 1, 2, 3, 4
 MEDIUM_NO_EMITTER_SAMPLING, MEDIUM_NO_SPECTRAL_EXTINCTION = 1, 2
 INTEGRATOR_PATH, INTEGRATOR_VOLPATH, INTEGRATOR_PRB, INTEGRATOR_PRBVOLPATH = 0, 1, 2, 3
 # differentiable parameter ids of mh_render_backward (texture index, or kind | medium / emitter)
@@ -103,6 +103,12 @@ class Medium(C.Structure):
                 ("bbox_max", f32 * 3), ("max_density", f32), ("pad1", f32)]
 
 
+class PhaseBlend(C.Structure):
+    """mh_phase_blend (mh_scene_set_phase_blend)."""
+    _fields_ = [("phase", u32 * 2), ("g", f32 * 2), ("weight", f32), ("grid_res", u32 * 3),
+                ("grid_to_local", f32 * 12), ("grid_data", PF)]
+
+
 class Sensor(C.Structure):
     _fields_ = [("to_world", f32 * 16), ("sample_to_camera", f32 * 16), ("near_clip", f32),
                 ("far_clip", f32), ("width", u32), ("height", u32), ("rfilter", u32),
@@ -144,7 +150,8 @@ EXPORTS = [
     "mh_render_forward", "mh_comm_unique_id", "mh_comm_create", "mh_comm_create_all", "mh_comm_destroy",
     "mh_comm_info", "mh_comm_reduce", "mh_scene_set_comm", "mh_scene_synchronize", "mh_render_sharded",
     "mh_render_backward_sharded", "mh_scene_update_emitter", "mh_scene_set_phase_table", "mh_phase_sample",
-    "mh_phase_eval",
+    "mh_phase_eval", "mh_scene_set_phase_blend", "mh_scene_set_phase_blend_table",
+    "mh_scene_update_phase_blend_weight", "mh_phase_sample_at", "mh_phase_eval_at",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -188,6 +195,11 @@ def lib():
     L.mh_scene_set_phase_table.argtypes = [vp, u32, u32, PF, PF]
     L.mh_phase_sample.argtypes = [vp, u32, u64, vp, vp, vp, u32]
     L.mh_phase_eval.argtypes = [vp, u32, u64, vp, vp, u32]
+    L.mh_scene_set_phase_blend.argtypes = [vp, u32, C.POINTER(PhaseBlend)]
+    L.mh_scene_set_phase_blend_table.argtypes = [vp, u32, u32, u32, PF, PF]
+    L.mh_scene_update_phase_blend_weight.argtypes = [vp, u32, PF, u64]
+    L.mh_phase_sample_at.argtypes = [vp, u32, u64, vp, vp, vp, vp, u32]
+    L.mh_phase_eval_at.argtypes = [vp, u32, u64, vp, vp, vp, u32]
     L.mh_render.argtypes = [vp, C.POINTER(Integrator), u32, u32, u32, u32, vp, u32, C.POINTER(Stats)]
     L.mh_develop.argtypes = [vp, vp, vp, u32]
     L.mh_render_samples.argtypes = [vp, C.POINTER(Integrator), u32, u32, u32, u32, vp, u32]

@@ -90,6 +90,14 @@ class SceneParameters:
                 v = torch.tensor(list(scene.emitter(idx).radiance), dtype=torch.float32)
             elif kind == "phase_table":
                 v = torch.from_numpy(scene.phase_tables[idx][1].copy())
+            elif kind == "blend_weight":
+                b = scene.phase_blends[idx]
+                v = (torch.tensor([float(b.value)], dtype=torch.float32) if b.data is None
+                     else torch.from_numpy(b.data.reshape(b.data.shape + (1,)).copy()))
+            elif kind == "blend_child_table":
+                v = torch.from_numpy(scene.phase_blends[idx[0]].children[idx[1]]["table"][1].copy())
+            elif kind == "blend_child_g":
+                v = torch.tensor([scene.phase_blends[idx[0]].children[idx[1]]["g"]], dtype=torch.float32)
             else:
                 continue
             if device is not None:
@@ -130,7 +138,7 @@ class SceneParameters:
     def param_id(self, k) -> int:
         """mh_render_backward parameter id (include/mitsuba_hip.h MH_PARAM_*)."""
         kind, idx = self._kind[k]
-        if kind == "phase_table":
+        if kind in ("phase_table", "blend_weight", "blend_child_table", "blend_child_g"):
             raise A.MitsubaHipError(f"'{k}' can be updated but is not differentiable in the hip_ad_rgb variant "
                                     "(phase function gradients are not implemented)")
         if kind in ("grid", "medium_sigma_t"):
@@ -165,6 +173,32 @@ class SceneParameters:
                 self.scene.phase_tables[idx] = phase_table(self.scene.phase_tables[idx][0], arr)
                 for h in self.scene._handles.values():
                     self.scene.upload_phase_table(h, idx)
+            elif kind == "blend_weight":
+                b = self.scene.phase_blends[idx]
+                if not np.all(np.isfinite(arr)):
+                    raise RuntimeError("hip_ad_rgb: a blendphase weight must be finite")
+                if b.data is None:
+                    b.value = np.float32(arr[0])
+                else:
+                    b.data[...] = arr.reshape(b.data.shape)
+                for h in self.scene._handles.values():
+                    A.check(L.mh_scene_update_phase_blend_weight(h, idx, arr.ctypes.data_as(A.PF), arr.size))
+            elif kind == "blend_child_table":
+                from .scene import phase_table
+                c = self.scene.phase_blends[idx[0]].children[idx[1]]
+                c["table"] = phase_table(c["table"][0], arr)
+                for h in self.scene._handles.values():
+                    A.check(L.mh_scene_set_phase_blend_table(h, idx[0], idx[1], c["table"][0].size,
+                                                             c["table"][0].ctypes.data_as(A.PF),
+                                                             c["table"][1].ctypes.data_as(A.PF)))
+            elif kind == "blend_child_g":
+                g = float(arr[0])
+                if g >= 1.0 or g <= -1.0:
+                    raise RuntimeError("The asymmetry parameter must lie in the interval (-1, 1)!")
+                self.scene.phase_blends[idx[0]].children[idx[1]]["g"] = float(np.float32(g))
+                for h in self.scene._handles.values():   # the blend again: tabulated children keep their tables
+                    rec = self.scene.phase_blends[idx[0]].record()
+                    A.check(L.mh_scene_set_phase_blend(h, idx[0], C.byref(rec)))
             elif kind in ("grid", "medium_sigma_t", "medium_albedo"):
                 m = self.scene.medium(idx)
                 if kind == "grid":

@@ -203,6 +203,63 @@ def phase_table(cost, values):
     return c, v
 
 
+_RAYLEIGH_DEPOLARIZATION = ("hip_ad_rgb: the rayleigh phase function is supported with depolarization = 0 "
+                            "only: otherwise its value differs from its sampling density and the sampling "
+                            "weight is not 1, which the volumetric integrators here do not carry")
+
+
+def _load_gridvolume(spec, what: str):
+    """A one-channel trilinear / clamp `gridvolume` (volumes/grid.cpp) as its
+    VolumeGrid and its to_world with use_grid_bbox applied; `what` names the
+    grid in the messages."""
+    from .volume import VolumeGrid
+    if "filename" in spec:
+        grid = VolumeGrid.read(spec["filename"])
+    elif "data" in spec:
+        grid = VolumeGrid(spec["data"])
+    elif "grid" in spec:
+        grid = spec["grid"]
+    else:
+        raise RuntimeError("gridvolume: specify 'filename', 'data' or 'grid'")
+    if grid.channel_count() != 1:
+        raise RuntimeError(f"hip_ad_rgb: {what} must have one channel")
+    if spec.get("filter_type", "trilinear") != "trilinear" or spec.get("wrap_mode", "clamp") != "clamp":
+        raise RuntimeError("hip_ad_rgb: gridvolume supports filter_type='trilinear', wrap_mode='clamp'")
+    T = _to_transform(spec.get("to_world"))
+    if spec.get("use_grid_bbox", False):
+        lo, hi = grid.bbox_min.astype(np.float64), grid.bbox_max.astype(np.float64)
+        T = T @ Transform4f.translate(lo) @ Transform4f.scale(hi - lo)
+    return grid, T
+
+
+class PhaseBlend:
+    """A blendphase (phase/blendphase.cpp) with two children, as stored by the
+    scene and handed to mh_scene_set_phase_blend: `children[i]` is a dict with
+    'phase' (A.PHASE_*), 'g' (float32; hg only) and 'table' ((cost, values) of a
+    tabphase child, else None); the weight of child 0 is `value` (float32) or a
+    grid: `data` (float32, shape (z, y, x)) with `to_local` (12 float32, world ->
+    [0, 1]^3)."""
+
+    def __init__(self, children, value=None, data=None, to_local=None):
+        self.children = children
+        self.value = value
+        self.data = data
+        self.to_local = to_local
+
+    def record(self) -> "A.PhaseBlend":
+        b = A.PhaseBlend()
+        for i, c in enumerate(self.children):
+            b.phase[i], b.g[i] = c["phase"], c["g"]
+        if self.data is None:
+            b.weight = float(self.value)
+        else:
+            z, y, x = self.data.shape
+            b.grid_res[:] = [x, y, z]
+            b.grid_to_local[:] = [float(v) for v in self.to_local]
+            b.grid_data = self.data.ctypes.data_as(A.PF)
+        return b
+
+
 class _Builder:
     """Accumulates flattened plugin records."""
 
@@ -229,6 +286,7 @@ class _Builder:
         self.grids: List[np.ndarray] = []
         self.n_grid = 0
         self.phase_tables: Dict[int, Any] = {}   # medium index -> (cost, values) of a tabphase
+        self.phase_blends: Dict[int, PhaseBlend] = {}   # medium index -> its blendphase
         self.environment = A.INVALID
         self.bbox_min = np.full(3, np.inf, np.float32)   # Scene::bbox() over the shapes
         self.bbox_max = np.full(3, -np.inf, np.float32)
@@ -352,14 +410,15 @@ class _Builder:
             if rho < 0.0 or rho >= 1.0:
                 raise RuntimeError("Depolarization factor must be between 0 and 1!")
             if rho != 0.0:
-                raise RuntimeError("hip_ad_rgb: the rayleigh phase function is supported with depolarization = 0 "
-                                   "only: otherwise its value differs from its sampling density and the sampling "
-                                   "weight is not 1, which the volumetric integrators here do not carry")
+                raise RuntimeError(_RAYLEIGH_DEPOLARIZATION)
             m.phase, m.g = A.PHASE_RAYLEIGH, 0.0
         elif ph.get("type") == "tabphase":
             m.phase, m.g = A.PHASE_TABULATED, 0.0
             self.phase_tables[len(self.media)] = phase_table(ph.get("cost"), ph.get("values"))
             self.params[name + ".phase_function.values"] = ("phase_table", len(self.media))
+        elif ph.get("type") == "blendphase":
+            m.phase, m.g = A.PHASE_BLEND, 0.0
+            self.phase_blends[len(self.media)] = self.blendphase(ph, name + ".phase_function", len(self.media))
         else:
             raise RuntimeError(f'Phase function plugin "{ph.get("type")}" is not available in the hip_ad_rgb variant')
         m.flags = ((0 if spec.get("sample_emitters", True) else A.MEDIUM_NO_EMITTER_SAMPLING) |
@@ -377,23 +436,7 @@ class _Builder:
         elif ty == "heterogeneous":
             if not isinstance(st, dict) or st.get("type") != "gridvolume":
                 raise RuntimeError("hip_ad_rgb: heterogeneous media need a 'gridvolume' sigma_t")
-            from .volume import VolumeGrid
-            if "filename" in st:
-                grid = VolumeGrid.read(st["filename"])
-            elif "data" in st:
-                grid = VolumeGrid(st["data"])
-            elif "grid" in st:
-                grid = st["grid"]
-            else:
-                raise RuntimeError("gridvolume: specify 'filename', 'data' or 'grid'")
-            if grid.channel_count() != 1:
-                raise RuntimeError("hip_ad_rgb: sigma_t grids must have one channel")
-            if st.get("filter_type", "trilinear") != "trilinear" or st.get("wrap_mode", "clamp") != "clamp":
-                raise RuntimeError("hip_ad_rgb: gridvolume supports filter_type='trilinear', wrap_mode='clamp'")
-            T = _to_transform(st.get("to_world"))
-            if st.get("use_grid_bbox", False):
-                lo, hi = grid.bbox_min.astype(np.float64), grid.bbox_max.astype(np.float64)
-                T = T @ Transform4f.translate(lo) @ Transform4f.scale(hi - lo)
+            grid, T = _load_gridvolume(st, "sigma_t grids")
             x, y, z = grid.size()
             m.type = A.MEDIUM_HETEROGENEOUS
             m.grid_res[:] = [x, y, z]
@@ -416,6 +459,66 @@ class _Builder:
         idx = len(self.media) - 1
         self.medium_ids[name] = idx
         return idx
+
+    # -- blendphase.cpp: two nested phase functions and the volume weight_0 ------------
+    def blendphase(self, ph, key: str, medium: int) -> PhaseBlend:
+        # blendphase.cpp:73-80: the nested phase objects in declaration order, whatever their names
+        # (every nested object but the volume that blendphase.cpp:86 reads by its name)
+        nested = [v for k, v in ph.items() if isinstance(v, dict) and k != "weight_0"]
+        if len(nested) < 2:
+            raise RuntimeError("BlendPhase: At least two child phase functions must be specified!")
+        if len(nested) > 2:
+            raise RuntimeError(f"hip_ad_rgb: blendphase supports exactly two child phase functions, not {len(nested)}")
+        children = []
+        for i, c in enumerate(nested):
+            ty, rec = c.get("type"), {"phase": A.PHASE_ISOTROPIC, "g": 0.0, "table": None}
+            if ty == "blendphase":
+                raise RuntimeError("hip_ad_rgb: a blendphase nested in a blendphase is not supported")
+            if ty == "hg":
+                g = float(c.get("g", 0.8))
+                if g >= 1.0 or g <= -1.0:
+                    raise RuntimeError("The asymmetry parameter must lie in the interval (-1, 1)!")
+                rec["phase"], rec["g"] = A.PHASE_HG, float(np.float32(g))
+                self.params[f"{key}.phase_{i}.g"] = ("blend_child_g", (medium, i))
+            elif ty == "rayleigh":
+                rho = float(c.get("depolarization", 0.0))
+                if rho < 0.0 or rho >= 1.0:
+                    raise RuntimeError("Depolarization factor must be between 0 and 1!")
+                if rho != 0.0:
+                    raise RuntimeError(_RAYLEIGH_DEPOLARIZATION)
+                rec["phase"] = A.PHASE_RAYLEIGH
+            elif ty == "tabphase":
+                rec["phase"], rec["table"] = A.PHASE_TABULATED, phase_table(c.get("cost"), c.get("values"))
+                self.params[f"{key}.phase_{i}.values"] = ("blend_child_table", (medium, i))
+            elif ty != "isotropic":
+                raise RuntimeError(f'Phase function plugin "{ty}" is not available in the hip_ad_rgb variant')
+            children.append(rec)
+        # blendphase.cpp:86: props.volume("weight_0") -- a float becomes a constant volume
+        w = ph.get("weight_0")
+        if w is None:
+            raise RuntimeError('Property "weight_0" has not been specified!')
+        if isinstance(w, dict) and w.get("type") == "gridvolume":
+            grid, T = _load_gridvolume(w, "a blendphase weight grid")
+            x, y, z = grid.size()
+            data = np.ascontiguousarray(np.asarray(grid.data, np.float32).reshape(z, y, x))
+            if not np.all(np.isfinite(data)):
+                raise RuntimeError("hip_ad_rgb: a blendphase weight must be finite")
+            self.params[key + ".weight_0.data"] = ("blend_weight", medium)
+            return PhaseBlend(children, data=data, to_local=_f32(np.linalg.inv(T.matrix)[:3, :].reshape(-1)))
+        if isinstance(w, dict):
+            if w.get("type") != "constvolume":
+                raise RuntimeError(f'hip_ad_rgb: a blendphase weight is a float, a constvolume or a gridvolume, '
+                                   f'not "{w.get("type")}"')
+            w = w.get("value")
+            if isinstance(w, dict):
+                w = w.get("value", w.get("color"))
+        v = np.asarray(w, np.float64).reshape(-1)
+        if v.size != 1 and not np.all(v == v[0]):
+            raise RuntimeError("hip_ad_rgb: a blendphase weight must have one channel")
+        if not np.isfinite(v[0]):
+            raise RuntimeError("hip_ad_rgb: a blendphase weight must be finite")
+        self.params[key + ".weight_0.value"] = ("blend_weight", medium)
+        return PhaseBlend(children, value=np.float32(v[0]))
 
     # -- infinite emitters (constant.cpp, directional.cpp) ---------------------------
     def infinite_emitter(self, spec, name: str):
@@ -611,6 +714,7 @@ class Scene:
         self.texels = cat(b.texels, 1, np.float32)
         self.grid = cat(b.grids, 1, np.float32)
         self.phase_tables = b.phase_tables
+        self.phase_blends = b.phase_blends
         d = A.SceneDesc()
         d.abi_version = A.ABI_VERSION
         d.sensor = sensor
@@ -682,6 +786,8 @@ class Scene:
             self._handles[device] = h
             for idx in self.phase_tables:
                 self.upload_phase_table(h, idx)
+            for idx in self.phase_blends:
+                self.upload_phase_blend(h, idx)
             self._streams[device] = None
         if stream is not None and self._streams.get(device) != stream:
             A.check(A.lib().mh_scene_set_stream(h, C.c_void_p(stream) if stream else None))
@@ -692,6 +798,18 @@ class Scene:
         """mh_scene_set_phase_table of medium `idx` (a tabphase) on handle `h`."""
         c, v = self.phase_tables[idx]
         A.check(A.lib().mh_scene_set_phase_table(h, idx, c.size, c.ctypes.data_as(A.PF), v.ctypes.data_as(A.PF)))
+
+    def upload_phase_blend(self, h, idx: int):
+        """mh_scene_set_phase_blend of medium `idx` (a blendphase) on handle `h`,
+        then its tabphase children's tables."""
+        L, b = A.lib(), self.phase_blends[idx]
+        rec = b.record()
+        A.check(L.mh_scene_set_phase_blend(h, idx, C.byref(rec)))
+        for i, c in enumerate(b.children):
+            if c["table"] is not None:
+                cost, values = c["table"]
+                A.check(L.mh_scene_set_phase_blend_table(h, idx, i, cost.size, cost.ctypes.data_as(A.PF),
+                                                         values.ctypes.data_as(A.PF)))
 
     def release(self):
         if self._handles:

@@ -126,6 +126,9 @@ class _Parser:
                 sub = self.obj(c)
                 if el.tag == "scene":
                     key = c.attrib.get("id") or (c.tag if c.tag in ("integrator", "sensor") else None)
+                elif el.tag == "phase" and c.tag == "phase" and name is None:
+                    # blendphase.cpp:73-80: the nested phase functions, in document order
+                    key = f"phase_{sum(1 for k in d if k.startswith('phase_'))}"
                 else:
                     key = name or _DEFAULT_SLOT.get(c.tag) or c.attrib.get("id")
                 if key is None:

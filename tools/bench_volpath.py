@@ -7,7 +7,9 @@ bench line: bench.py measures BASELINE.json's headline metric).
 --phase replaces the medium's HG (g = 0.85) by `rayleigh`, or by `tab`: the same
 HG tabulated for `tabphase` on 1,801 cosines of a grid uniform in angle (0.1
 degree), the size of a Mie table; the difference to hg is the cost of the
-table searches.  The CPU oracle has neither, so these runs skip its baseline."""
+table searches; or by `blend`: a `blendphase` of `rayleigh` (air) and that table
+(aerosol), the table's weight falling with height on a 64^3 grid of its own.
+The CPU oracle has none of them, so these runs skip its baseline."""
 import argparse
 import json
 import os
@@ -28,6 +30,14 @@ def phase_spec(name):
         g = 0.85
         return {"type": "tabphase", "cost": c,
                 "values": (1 - g * g) / (4 * np.pi * (1 + g * g - 2 * g * c) ** 1.5)}
+    if name == "blend":
+        import numpy as np
+        from mitsuba_hip import Transform4f as T
+        # child 0 = rayleigh: its weight rises with height (y), the aerosol's falls
+        w = np.broadcast_to(np.linspace(0.1, 0.9, 64, dtype=np.float32)[None, :, None], (64, 64, 64))
+        return {"type": "blendphase", "air": {"type": "rayleigh"}, "aerosol": phase_spec("tab"),
+                "weight_0": {"type": "gridvolume", "data": np.ascontiguousarray(w),
+                             "to_world": T.translate([-1.0, -1.0, -1.0]) @ T.scale([2.0, 2.0, 2.0])}}
     return {"type": "hg", "g": 0.85}
 
 
@@ -45,8 +55,9 @@ def main():
                     help="prbvolpath: MH_FLAG_DETERMINISTIC backward (int64 fixed-point grid + albedo gradients)")
     ap.add_argument("--overlap", action="store_true",
                     help="prbvolpath: forward || backward on two scene handles and streams (grad_in is constant)")
-    ap.add_argument("--phase", default="hg", choices=["hg", "rayleigh", "tab"],
-                    help="the medium's phase function: hg (g = 0.85), rayleigh, or that hg as an 1,801-node tabphase")
+    ap.add_argument("--phase", default="hg", choices=["hg", "rayleigh", "tab", "blend"],
+                    help="the medium's phase function: hg (g = 0.85), rayleigh, that hg as an 1,801-node tabphase, "
+                         "or a blendphase of rayleigh and that table with a 64^3 weight grid")
     a = ap.parse_args()
     a.no_cpu = a.no_cpu or a.phase != "hg"   # the oracle has only isotropic and hg
     import torch
