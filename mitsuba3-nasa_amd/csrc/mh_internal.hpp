@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/mitsuba_hip.h"
+#include "mh_variant.hpp"
 
 namespace mh {
 
@@ -127,6 +128,7 @@ uint32_t wf_grid(uint32_t grid);
 uint32_t wf_blocks(int cus, bool shared = false);  // wavefront workgroups for a device of `cus` CUs (shared: another call runs beside)
 uint32_t wf_packet_max_prims();  // largest scene (primitives) the packet engine traces
 bool wf_fused(const DScene &S);  // launch_wavefront runs the fused bounce kernel  // grid rounded to whole queue segments
+variant::Facts variant_facts(const DScene &S);  // what the kernel-variant selectors read of a scene and the environment
 // One bitmap parameter on the fused PRB wavefront: the bounce kernel logs a
 // record per bitmap vertex, a scatter pass turns the records into texel
 // gradients once the chunk's paths have ended (mh_wavefront.hip).

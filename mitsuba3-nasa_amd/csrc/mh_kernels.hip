@@ -925,18 +925,15 @@ hipError_t launch_trace(const DScene &S, bool shadow, uint64_t n, const float *r
     const uint32_t bs = 256;
     uint32_t g = grid ? grid : blocks_for(n, bs);
     if (g == 0) return hipSuccess;
-    const bool lds = S.lds_bytes_bvh != 0, stream = !lds && (S.qnodes || S.nodes4);
+    const bool lds = variant_facts(S).bvh_lds, stream = !lds && (S.qnodes || S.nodes4);
     if (stream && n >= (1ull << 32)) return hipErrorInvalidValue;  // 32-bit stream items
     // the stream engine: its LDS stack, and at most one overflow column per thread
     if (stream && S.stack_ovf) g = std::min<uint32_t>(g, S.ovf_threads / bs);
     const size_t sh = stream ? stream_lds_bytes(S, bs) : lds_bytes(S, bs);
-    if (shadow) {
-        if (lds) hipLaunchKernelGGL(k_trace_shadow<true>, dim3(g), dim3(bs), sh, st, S, n, rays, occ);
-        else hipLaunchKernelGGL(k_trace_shadow<false>, dim3(g), dim3(bs), sh, st, S, n, rays, occ);
-    } else {
-        if (lds) hipLaunchKernelGGL(k_trace_closest<true>, dim3(g), dim3(bs), sh, st, S, n, rays, t, u, v, prim, shape, inst);
-        else hipLaunchKernelGGL(k_trace_closest<false>, dim3(g), dim3(bs), sh, st, S, n, rays, t, u, v, prim, shape, inst);
-    }
+    variant::select([&](auto L) {
+        if (shadow) hipLaunchKernelGGL(k_trace_shadow<L>, dim3(g), dim3(bs), sh, st, S, n, rays, occ);
+        else hipLaunchKernelGGL(k_trace_closest<L>, dim3(g), dim3(bs), sh, st, S, n, rays, t, u, v, prim, shape, inst);
+    }, variant::flag(lds));
     return hipGetLastError();
 }
 
@@ -993,28 +990,10 @@ hipError_t launch_render(const DScene &S, const IntegratorParams &in, const Lane
     const uint32_t bs = 256;
     size_t sh = lds_bytes(S, bs);
     if (n == 0) return hipSuccess;
-    const bool lds = S.lds_bytes_bvh != 0;
     const dim3 g(blocks_for(n, bs)), b(bs);
-#define MH_LAUNCH_RENDER(K)                                                                                   \
-    do {                                                                                                      \
-        if (lds) hipLaunchKernelGGL((k_render<K, true>), g, b, sh, st, S, in, lm, seed_value, n_passes, n, plane, out, counters, alpha); \
-        else hipLaunchKernelGGL((k_render<K, false>), g, b, sh, st, S, in, lm, seed_value, n_passes, n, plane, out, counters, alpha);    \
-    } while (0)
-    // a scene with a blend medium: the volumetric kernels compiled with blendphase
-#define MH_LAUNCH_RENDER_BLEND(K)                                                                             \
-    do {                                                                                                      \
-        if (lds) hipLaunchKernelGGL((k_render<K, true, kPhBlend>), g, b, sh, st, S, in, lm, seed_value, n_passes, n, plane, out, counters, alpha); \
-        else hipLaunchKernelGGL((k_render<K, false, kPhBlend>), g, b, sh, st, S, in, lm, seed_value, n_passes, n, plane, out, counters, alpha);    \
-    } while (0)
-    const bool blend = S.vol_flags & kVolPhaseBlend;
-    if (in.type == MH_INTEGRATOR_PRB) MH_LAUNCH_RENDER(MH_INTEGRATOR_PRB);
-    else if (in.type == MH_INTEGRATOR_VOLPATH && blend) MH_LAUNCH_RENDER_BLEND(MH_INTEGRATOR_VOLPATH);
-    else if (in.type == MH_INTEGRATOR_VOLPATH) MH_LAUNCH_RENDER(MH_INTEGRATOR_VOLPATH);
-    else if (in.type == MH_INTEGRATOR_PRBVOLPATH && blend) MH_LAUNCH_RENDER_BLEND(MH_INTEGRATOR_PRBVOLPATH);
-    else if (in.type == MH_INTEGRATOR_PRBVOLPATH) MH_LAUNCH_RENDER(MH_INTEGRATOR_PRBVOLPATH);
-    else MH_LAUNCH_RENDER(MH_INTEGRATOR_PATH);
-#undef MH_LAUNCH_RENDER_BLEND
-#undef MH_LAUNCH_RENDER
+    variant::render(variant_facts(S), in.type, [&](auto K, auto L, auto Ph) {
+        hipLaunchKernelGGL((k_render<K, L, Ph>), g, b, sh, st, S, in, lm, seed_value, n_passes, n, plane, out, counters, alpha);
+    });
     return hipGetLastError();
 }
 
@@ -1024,15 +1003,10 @@ hipError_t launch_render_forward(const DScene &S, const IntegratorParams &in, co
     const uint32_t bs = 256;
     if (n == 0) return hipSuccess;
     const size_t sh = lds_bytes(S, bs);
-    const bool lds = S.lds_bytes_bvh != 0, vol = in.type == MH_INTEGRATOR_PRBVOLPATH;
     const dim3 g(blocks_for(n, bs)), b(bs);
-    const bool blend = vol && (S.vol_flags & kVolPhaseBlend);
-    if (blend && lds) hipLaunchKernelGGL((k_render_forward<true, true, kPhBlend>), g, b, sh, st, S, in, lm, seed_value, n, plane, out, ga, counters, alpha);
-    else if (blend) hipLaunchKernelGGL((k_render_forward<true, false, kPhBlend>), g, b, sh, st, S, in, lm, seed_value, n, plane, out, ga, counters, alpha);
-    else if (vol && lds) hipLaunchKernelGGL((k_render_forward<true, true>), g, b, sh, st, S, in, lm, seed_value, n, plane, out, ga, counters, alpha);
-    else if (vol) hipLaunchKernelGGL((k_render_forward<true, false>), g, b, sh, st, S, in, lm, seed_value, n, plane, out, ga, counters, alpha);
-    else if (lds) hipLaunchKernelGGL((k_render_forward<false, true>), g, b, sh, st, S, in, lm, seed_value, n, plane, out, ga, counters, alpha);
-    else hipLaunchKernelGGL((k_render_forward<false, false>), g, b, sh, st, S, in, lm, seed_value, n, plane, out, ga, counters, alpha);
+    variant::render_forward(variant_facts(S), in.type, [&](auto Vol, auto L, auto Ph) {
+        hipLaunchKernelGGL((k_render_forward<Vol, L, Ph>), g, b, sh, st, S, in, lm, seed_value, n, plane, out, ga, counters, alpha);
+    });
     return hipGetLastError();
 }
 
@@ -1052,54 +1026,37 @@ hipError_t launch_splat(const DScene &S, const LaneMap &lm, int mode, bool fast,
     if (mode != kSplatWeights &&
         (plane < (uint64_t)n_passes * n || in_floats < (uint64_t)(mode == kSplatAlpha ? 6 : 5) * plane || !in))
         return hipErrorInvalidValue;
-#define MH_SPLAT_PX(M)                                                                                          \
-    hipLaunchKernelGGL(k_splat_px<M>, dim3(blocks_for(lanes, bs)), dim3(bs), 0, st, S, lm.pixel_begin, n_pix, \
-                       lm.S, n_passes, n, plane, in, film, seed_value, lm.spp_pp, lm.s_begin, invalid, in_floats, viol)
-#define MH_SPLAT_GEN(M)                                                                                         \
-    hipLaunchKernelGGL(k_splat_generic<M>, dim3(blocks_for(n, bs)), dim3(bs), 0, st, S, lm, n_passes, n, plane, \
-                       in, film, seed_value, coalesce, invalid)
-#define MH_SPLAT_GATHER(M)                                                                                      \
-    hipLaunchKernelGGL(k_splat_gather<M>, dim3(blocks_for((uint64_t)n_rows * S.width, 256)), dim3(256), 0, st, S, \
-                       lm.pixel_begin, n_pix, row0, n_rows, lm.S, n_passes, n, plane, in, film, seed_value,      \
-                       lm.spp_pp, lm.s_begin)
-    if (fast && deterministic) {
-        // film rows the chunk's footprints reach: its first row - 2 .. its last row + 3
-        const uint32_t r_first = lm.pixel_begin / S.width, r_last = (lm.pixel_begin + n_pix - 1) / S.width;
-        const uint32_t row0 = r_first >= 2 ? r_first - 2 : 0, row1 = std::min<uint32_t>(S.height - 1, r_last + 3);
-        const uint32_t n_rows = row1 - row0 + 1;
-        if (mode == kSplatWeights) MH_SPLAT_GATHER(1);
-        else if (mode == kSplatAlpha) MH_SPLAT_GATHER(2);
-        else MH_SPLAT_GATHER(0);
-        if (mode == kSplatFilm && invalid)  // the sample check of the atomic path, counted by the generic kernel's rule
-            hipLaunchKernelGGL(k_count_invalid, dim3(blocks_for(n * n_passes, 256)), dim3(256), 0, st, n * n_passes,
-                               n, plane, in, invalid);
-    } else if (fast && (mode == kSplatFilm || mode == kSplatWeights) && MH_SPLAT_TILE) {
-        const uint32_t r_first = lm.pixel_begin / S.width, r_last = (lm.pixel_begin + n_pix - 1) / S.width;
-        const uint32_t tiles_x = (S.width + kSplatTile - 1) / kSplatTile;
-        const uint32_t tiles_y = (r_last - r_first + 1 + kSplatTile - 1) / kSplatTile;
-        if (mode == kSplatFilm)
-            hipLaunchKernelGGL(k_splat_tile<0>, dim3(tiles_x * tiles_y), dim3(256), 0, st, S, lm.pixel_begin, n_pix,
-                               r_first, tiles_x, lm.S, n_passes, n, plane, in, film, invalid, in_floats, viol,
-                               seed_value, lm.spp_pp, lm.s_begin);
-        else
-            hipLaunchKernelGGL(k_splat_tile<1>, dim3(tiles_x * tiles_y), dim3(256), 0, st, S, lm.pixel_begin, n_pix,
-                               r_first, tiles_x, lm.S, n_passes, n, plane, in, film, invalid, in_floats, viol,
-                               seed_value, lm.spp_pp, lm.s_begin);
-    } else if (fast) {
-        const uint32_t bs = 128;
-        const uint64_t lanes = (uint64_t)n_pix * kSplatLanes;
-        if (mode == kSplatWeights) MH_SPLAT_PX(1);
-        else if (mode == kSplatAlpha) MH_SPLAT_PX(2);
-        else MH_SPLAT_PX(0);
-    } else {
-        const uint32_t bs = 256;
-        if (mode == kSplatWeights) MH_SPLAT_GEN(1);
-        else if (mode == kSplatAlpha) MH_SPLAT_GEN(2);
-        else MH_SPLAT_GEN(0);
-    }
-#undef MH_SPLAT_PX
-#undef MH_SPLAT_GEN
-#undef MH_SPLAT_GATHER
+    variant::select([&](auto M) {  // M: the kernels' mode
+        if (fast && deterministic) {
+            // film rows the chunk's footprints reach: its first row - 2 .. its last row + 3
+            const uint32_t r_first = lm.pixel_begin / S.width, r_last = (lm.pixel_begin + n_pix - 1) / S.width;
+            const uint32_t row0 = r_first >= 2 ? r_first - 2 : 0, row1 = std::min<uint32_t>(S.height - 1, r_last + 3);
+            const uint32_t n_rows = row1 - row0 + 1;
+            hipLaunchKernelGGL(k_splat_gather<M>, dim3(blocks_for((uint64_t)n_rows * S.width, 256)), dim3(256), 0, st, S,
+                               lm.pixel_begin, n_pix, row0, n_rows, lm.S, n_passes, n, plane, in, film, seed_value,
+                               lm.spp_pp, lm.s_begin);
+            if (mode == kSplatFilm && invalid)  // the sample check of the atomic path, counted by the generic kernel's rule
+                hipLaunchKernelGGL(k_count_invalid, dim3(blocks_for(n * n_passes, 256)), dim3(256), 0, st, n * n_passes,
+                                   n, plane, in, invalid);
+        } else if (fast && (mode == kSplatFilm || mode == kSplatWeights) && MH_SPLAT_TILE) {
+            const uint32_t r_first = lm.pixel_begin / S.width, r_last = (lm.pixel_begin + n_pix - 1) / S.width;
+            const uint32_t tiles_x = (S.width + kSplatTile - 1) / kSplatTile;
+            const uint32_t tiles_y = (r_last - r_first + 1 + kSplatTile - 1) / kSplatTile;
+            if constexpr (M != kSplatAlpha)  // (the tile kernel has no alpha mode)
+                hipLaunchKernelGGL(k_splat_tile<M>, dim3(tiles_x * tiles_y), dim3(256), 0, st, S, lm.pixel_begin, n_pix,
+                                   r_first, tiles_x, lm.S, n_passes, n, plane, in, film, invalid, in_floats, viol,
+                                   seed_value, lm.spp_pp, lm.s_begin);
+        } else if (fast) {
+            const uint32_t bs = 128;
+            const uint64_t lanes = (uint64_t)n_pix * kSplatLanes;
+            hipLaunchKernelGGL(k_splat_px<M>, dim3(blocks_for(lanes, bs)), dim3(bs), 0, st, S, lm.pixel_begin, n_pix,
+                               lm.S, n_passes, n, plane, in, film, seed_value, lm.spp_pp, lm.s_begin, invalid, in_floats, viol);
+        } else {
+            const uint32_t bs = 256;
+            hipLaunchKernelGGL(k_splat_generic<M>, dim3(blocks_for(n, bs)), dim3(bs), 0, st, S, lm, n_passes, n, plane,
+                               in, film, seed_value, coalesce, invalid);
+        }
+    }, variant::among<0, 1, 2>(mode == kSplatWeights ? 1 : mode == kSplatAlpha ? 2 : 0));
     return hipGetLastError();
 }
 
@@ -1293,14 +1250,9 @@ hipError_t launch_accumulate(float *dst, const float *src, uint64_t n, hipStream
 hipError_t launch_develop(uint64_t n_px, const float *film, float *rgb, uint32_t fmt, hipStream_t st) {
     if (n_px == 0) return hipSuccess;
     const dim3 g(blocks_for(n_px, 256)), b(256);
-    switch (fmt) {
-    case MH_PIXEL_Y: hipLaunchKernelGGL((k_develop<MH_PIXEL_Y, false>), g, b, 0, st, n_px, film, rgb); break;
-    case MH_PIXEL_XYZ: hipLaunchKernelGGL((k_develop<MH_PIXEL_XYZ, false>), g, b, 0, st, n_px, film, rgb); break;
-    case MH_PIXEL_RGBA: hipLaunchKernelGGL((k_develop<MH_PIXEL_RGB, true>), g, b, 0, st, n_px, film, rgb); break;
-    case MH_PIXEL_YA: hipLaunchKernelGGL((k_develop<MH_PIXEL_Y, true>), g, b, 0, st, n_px, film, rgb); break;
-    case MH_PIXEL_XYZA: hipLaunchKernelGGL((k_develop<MH_PIXEL_XYZ, true>), g, b, 0, st, n_px, film, rgb); break;
-    default: hipLaunchKernelGGL((k_develop<MH_PIXEL_RGB, false>), g, b, 0, st, n_px, film, rgb);
-    }
+    variant::develop(fmt, [&](auto Fmt, auto Alpha) {
+        hipLaunchKernelGGL((k_develop<Fmt, Alpha>), g, b, 0, st, n_px, film, rgb);
+    });
     return hipGetLastError();
 }
 
@@ -1315,37 +1267,9 @@ hipError_t launch_prb_backward(const DScene &S, const IntegratorParams &in, cons
     size_t sh = lds_bytes(S, bs);
     dim3 g(blocks_for(n, bs)), b(bs);
     GradArgs ga = ga_in;
-    if (in.type != MH_INTEGRATOR_PRBVOLPATH && !fused && ga.lds_slot >= 0) {
-        // persistent grid: as many workgroups as fit beside the texel accumulator
-        // the accumulator must fit the device's per-workgroup LDS beside the
-        // BVH / stack staging; otherwise the texels take the global-atomic path
-        int dev = 0, cus = 256, max_wg = 64 << 10, per_cu_lds = 160 << 10;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        (void)hipDeviceGetAttribute(&max_wg, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
-        (void)hipDeviceGetAttribute(&per_cu_lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev);
-        // the kernel's static LDS (GradCtx's per-wave fixed-point sums,
-        // g_fx_wave) comes on top of the dynamic bytes
-        hipFuncAttributes fa{};
-        const bool em = ga.emitter_off != 0;  // (fused is false here)
-        const void *fn = S.lds_bytes_bvh ? (em ? (const void *)k_prb_backward<true, false, true> : (const void *)k_prb_backward<true, false>)
-                                         : (em ? (const void *)k_prb_backward<false, false, true> : (const void *)k_prb_backward<false, false>);
-        const size_t st_lds = hipFuncGetAttributes(&fa, fn) == hipSuccess ? fa.sharedSizeBytes : (size_t)kFxStaticLdsBytes;
-        const uint32_t off = (uint32_t)((sh + 15) / 16 * 16);
-        const size_t total = off + (size_t)ga.lds_floats * 4;
-        if (total + st_lds <= (size_t)max_wg) {
-            ga.lds_offset = off;
-            sh = total;
-            const size_t lds_cu = per_cu_lds > 0 ? (size_t)per_cu_lds : (size_t)max_wg;
-            const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(4, lds_cu / (sh + st_lds)));
-            g = dim3(std::min<uint32_t>(blocks_for(n, bs), (uint32_t)cus * per_cu));
-        } else {
-            ga.lds_slot = -1;
-        }
-    } else {
-        ga.lds_slot = -1;
-    }
+    const variant::Facts F = variant_facts(S);
     if (in.type == MH_INTEGRATOR_PRBVOLPATH) {
+        ga.lds_slot = -1;
         PvpWork wk{nullptr, 0, nullptr, nullptr, 0};
         if (nee_log && head && nee_cap && nee_blocks) {
             wk = PvpWork{nee_log, nee_cap, head, main_cap ? main_log : nullptr, main_cap};
@@ -1353,31 +1277,42 @@ hipError_t launch_prb_backward(const DScene &S, const IntegratorParams &in, cons
             hipError_t e = hipMemsetAsync(head, 0, sizeof(unsigned long long), st);
             if (e != hipSuccess) return e;
         }
-        const bool blend = S.vol_flags & kVolPhaseBlend;
-        if (S.lds_bytes_bvh && blend)
-            hipLaunchKernelGGL((k_prbvol_backward<true, kPhBlend>), g, b, sh, st, S, in, lm, seed_value, n, coalesce, grad_in, ga, counters, wk);
-        else if (blend)
-            hipLaunchKernelGGL((k_prbvol_backward<false, kPhBlend>), g, b, sh, st, S, in, lm, seed_value, n, coalesce, grad_in, ga, counters, wk);
-        else if (S.lds_bytes_bvh)
-            hipLaunchKernelGGL((k_prbvol_backward<true>), g, b, sh, st, S, in, lm, seed_value, n, coalesce, grad_in, ga, counters, wk);
-        else
-            hipLaunchKernelGGL((k_prbvol_backward<false>), g, b, sh, st, S, in, lm, seed_value, n, coalesce, grad_in, ga, counters, wk);
-    } else {
-#define MH_PRB_BACKWARD(LDS, FUSED, EM)                                                                          \
-    hipLaunchKernelGGL((k_prb_backward<LDS, FUSED, EM>), g, b, sh, st, S, in, lm, seed_value, n, coalesce, grad_in, \
-                       weights, ga, counters)
-#define MH_PRB_BACKWARD_EM(LDS, FUSED)                                                                           \
-    do {                                                                                                         \
-        if (ga.emitter_off) MH_PRB_BACKWARD(LDS, FUSED, true);                                                   \
-        else MH_PRB_BACKWARD(LDS, FUSED, false);                                                                 \
-    } while (0)
-        if (S.lds_bytes_bvh && fused) MH_PRB_BACKWARD_EM(true, true);
-        else if (S.lds_bytes_bvh) MH_PRB_BACKWARD_EM(true, false);
-        else if (fused) MH_PRB_BACKWARD_EM(false, true);
-        else MH_PRB_BACKWARD_EM(false, false);
-#undef MH_PRB_BACKWARD_EM
-#undef MH_PRB_BACKWARD
+        variant::dispatch(variant::vol_lane(F), [&](auto, auto Ph, auto L, auto, auto) {
+            hipLaunchKernelGGL((k_prbvol_backward<L, Ph>), g, b, sh, st, S, in, lm, seed_value, n, coalesce, grad_in, ga, counters, wk);
+        });
+        return hipGetLastError();
     }
+    variant::select([&](auto L, auto Fused, auto Em) {
+        bool acc = !Fused && ga.lds_slot >= 0;  // the replay kernel's LDS texel accumulator
+        if (acc) {
+            // persistent grid: as many workgroups as fit beside the texel accumulator
+            // the accumulator must fit the device's per-workgroup LDS beside the
+            // BVH / stack staging; otherwise the texels take the global-atomic path
+            int dev = 0, cus = 256, max_wg = 64 << 10, per_cu_lds = 160 << 10;
+            (void)hipGetDevice(&dev);
+            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+            (void)hipDeviceGetAttribute(&max_wg, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+            (void)hipDeviceGetAttribute(&per_cu_lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev);
+            // the launched instance's static LDS (GradCtx's per-wave fixed-point
+            // sums, g_fx_wave) comes on top of the dynamic bytes
+            hipFuncAttributes fa{};
+            const void *fn = reinterpret_cast<const void *>(&k_prb_backward<L, Fused, Em>);
+            const size_t st_lds = hipFuncGetAttributes(&fa, fn) == hipSuccess ? fa.sharedSizeBytes : (size_t)kFxStaticLdsBytes;
+            const uint32_t off = (uint32_t)((sh + 15) / 16 * 16);
+            const size_t total = off + (size_t)ga.lds_floats * 4;
+            acc = total + st_lds <= (size_t)max_wg;
+            if (acc) {
+                ga.lds_offset = off;
+                sh = total;
+                const size_t lds_cu = per_cu_lds > 0 ? (size_t)per_cu_lds : (size_t)max_wg;
+                const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(4, lds_cu / (sh + st_lds)));
+                g = dim3(std::min<uint32_t>(blocks_for(n, bs), (uint32_t)cus * per_cu));
+            }
+        }
+        if (!acc) ga.lds_slot = -1;
+        hipLaunchKernelGGL((k_prb_backward<L, Fused, Em>), g, b, sh, st, S, in, lm, seed_value, n, coalesce, grad_in,
+                           weights, ga, counters);
+    }, variant::flag(F.bvh_lds), variant::flag(fused), variant::flag(ga.emitter_off != 0));
     return hipGetLastError();
 }
 

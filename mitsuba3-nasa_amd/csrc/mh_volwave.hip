@@ -43,6 +43,7 @@
 //                  W3 pcg.state lo hi, pcg_v1
 #include <algorithm>
 #include <cstring>
+#include <tuple>
 #include <type_traits>
 
 #include "mh_env.hpp"
@@ -1883,13 +1884,6 @@ k_vol_sched(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value, uin
 bool vol_sched_mode() { return !env::vol_mode_rounds(); }
 // one resident round of 256-lane workgroups (a wave per SIMD each)
 uint32_t vs_blocks(int cus) { return (uint32_t)cus * (uint32_t)env::vs_bpc(MH_VS_WAVES); }
-// the traversal engine of a launch: wave-coherent packets for scenes with pair
-// records (MH_TRAVERSAL=lane: per-lane)
-static bool vol_packet(const DScene &S) {
-    return S.n_prims > 0 && S.n_prims <= wf_packet_max_prims() && !env::traversal_lane();
-}
-// the phase scheduler's LDS shading tables
-static bool vs_tables(const DScene &S) { return S.tab_bytes != 0 && !env::vs_notab(); }
 uint64_t vw_max_chunk() { return 1ull << 23; }
 size_t vw_workspace_bytes(uint64_t cap) { return (size_t)2 * kVwPlanes * 16 * cap; }
 uint32_t vw_counter_words(uint32_t rounds) { return kVwCtr * (rounds + 1); }
@@ -1905,62 +1899,6 @@ bool vs_supported(const DScene &S, const IntegratorParams &in) {
 }
 uint32_t vw_blocks(int cus) {
     return std::max<uint32_t>(kVwSeg, (uint32_t)cus * (uint32_t)env::vw_bpc(8) / kVwSeg * kVwSeg);
-}
-
-// the launch's scene: with the phase tables staged (the kernels with the LDS
-// tables only) where plan::phase_lds_bytes finds room beside the launch's
-// dynamic LDS and the static LDS of the kernel instance that stages them (M's
-// <false, true, true>; the runtime's figure, so the machines' arrays may grow).
-// -DMH_PHASE_LDS=0 builds keep the tables in global memory (A/B).
-#ifndef MH_PHASE_LDS
-#define MH_PHASE_LDS 1
-#endif
-template <class M>
-static hipError_t vs_launch_scene(const DScene &S0, bool pk, bool tab, DScene &S) {
-    S = S0;
-    S.phase_lds_bytes = 0;
-    if (!MH_PHASE_LDS || !pk || !tab || !S.phase_tab_bytes) return hipSuccess;
-    hipFuncAttributes fa;
-    hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_vol_sched<M, false, true, true>));
-    if (e != hipSuccess) return e;
-    S.phase_lds_bytes = plan::phase_lds_bytes(S.phase_tab_bytes, lds_bytes(S, 256) + vs_tab_bytes(S) +
-                                                                     vs_defer_bytes(S) + fa.sharedSizeBytes);
-    return hipSuccess;
-}
-
-hipError_t launch_vol_sched(const DScene &S0, const IntegratorParams &in, const LaneMap &lm, uint32_t seed_value,
-                            uint64_t n, uint64_t plane, float *out, uint32_t grid, unsigned long long *counters,
-                            hipStream_t st, int alpha) {
-    if (n == 0) return hipSuccess;
-    const bool pk = vol_packet(S0), tab = vs_tables(S0);
-    DScene S;
-    const bool blend = S0.vol_flags & kVolPhaseBlend, pv = in.type == MH_INTEGRATOR_PRBVOLPATH;
-    hipError_t e = pv ? (blend ? vs_launch_scene<PvMachineBlend>(S0, pk, tab, S) : vs_launch_scene<PvMachine>(S0, pk, tab, S))
-                      : (blend ? vs_launch_scene<VolMachineBlend>(S0, pk, tab, S) : vs_launch_scene<VolMachine>(S0, pk, tab, S));
-    if (e != hipSuccess) return e;
-    const size_t sh = lds_bytes(S, 256);
-    const bool lds = S.lds_bytes_bvh != 0;
-#define MH_VS1(Mc, L, P, T)                                                                                   \
-    hipLaunchKernelGGL((k_vol_sched<Mc, L, P, T>), dim3(grid), dim3(256), sh + (T ? vs_tab_bytes(S) : 0u) + (P ? vs_defer_bytes(S) : 0u), st, S, \
-                       in, lm, seed_value, n, plane, out, counters, work, alpha, VsBwdArgs{})
-#define MH_VS(L, P, T)                                                  \
-    do {                                                                \
-        if (pv && blend) MH_VS1(PvMachineBlend, L, P, T);               \
-        else if (pv) MH_VS1(PvMachine, L, P, T);                        \
-        else if (blend) MH_VS1(VolMachineBlend, L, P, T);               \
-        else if (S.vol_flags & kVolPhaseExt) MH_VS1(VolMachine, L, P, T); \
-        else MH_VS1(VolMachineHg, L, P, T);                             \
-    } while (0)
-    unsigned long long *work = counters + 32;  // the 8 queue heads of this launch (128 B apart)
-    e = hipMemsetAsync(work, 0, 8 * 128, st);
-    if (e != hipSuccess) return e;
-    if (pk && tab) MH_VS(false, true, true);
-    else if (pk) MH_VS(false, true, false);
-    else if (lds) MH_VS(true, false, false);
-    else MH_VS(false, false, false);
-#undef MH_VS
-#undef MH_VS1
-    return hipGetLastError();
 }
 
 // PvBwdMachine for a call that lists an emitter's radiance
@@ -2014,43 +1952,60 @@ extern "C" int mh_exp_vs_sub(unsigned long long *out, int reset) {
 }
 #endif
 
+// k_vol_sched's instance for `key` on the launch's scene: S0 with the phase
+// tables staged (the kernels with the LDS tables only) where plan::phase_lds_bytes
+// finds room beside the launch's dynamic LDS and the instance's own static LDS (the
+// runtime's figure, so the machines' arrays may grow).  -DMH_PHASE_LDS=0: global memory (A/B).
+#ifndef MH_PHASE_LDS
+#define MH_PHASE_LDS 1
+#endif
+using VsMachines = std::tuple<VolMachineHg, VolMachine, VolMachineBlend, PvMachine, PvMachineBlend, PvBwdMachine,
+                              PvBwdMachineBlend, PvBwdMachineEm, PvBwdMachineEmBlend>;  // by variant::Machine
+static hipError_t vs_launch(const variant::VolSched &key, const DScene &S0, const IntegratorParams &in,
+                            const LaneMap &lm, uint32_t seed_value, uint64_t n, uint64_t plane, float *out,
+                            uint32_t grid, unsigned long long *counters, hipStream_t st, int alpha,
+                            const VsBwdArgs &bw) {
+    hipError_t e = hipErrorInvalidValue;
+    variant::dispatch(key, [&](auto m, auto L, auto P, auto T) {
+        using M = std::tuple_element_t<decltype(m)::value, VsMachines>;
+        DScene S = S0;
+        S.phase_lds_bytes = 0;
+        if (MH_PHASE_LDS && T && S.phase_tab_bytes) {
+            hipFuncAttributes fa;
+            e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_vol_sched<M, L, P, T>));
+            if (e != hipSuccess) return;
+            S.phase_lds_bytes = plan::phase_lds_bytes(S.phase_tab_bytes, lds_bytes(S, 256) + vs_tab_bytes(S) +
+                                                                             vs_defer_bytes(S) + fa.sharedSizeBytes);
+        }
+        const size_t sh = lds_bytes(S, 256);
+        unsigned long long *work = counters + 32;  // the 8 queue heads of this launch (128 B apart)
+        e = hipMemsetAsync(work, 0, 8 * 128, st);
+        if (e != hipSuccess) return;
+        hipLaunchKernelGGL((k_vol_sched<M, L, P, T>), dim3(grid), dim3(256), sh + (T ? vs_tab_bytes(S) : 0u) + (P ? vs_defer_bytes(S) : 0u), st, S,
+                           in, lm, seed_value, n, plane, out, counters, work, alpha, bw);
+        e = hipGetLastError();
+    });
+    return e;
+}
+
+hipError_t launch_vol_sched(const DScene &S, const IntegratorParams &in, const LaneMap &lm, uint32_t seed_value,
+                            uint64_t n, uint64_t plane, float *out, uint32_t grid, unsigned long long *counters,
+                            hipStream_t st, int alpha) {
+    if (n == 0) return hipSuccess;
+    return vs_launch(variant::vol_sched(variant_facts(S), in.type), S, in, lm, seed_value, n, plane, out, grid,
+                     counters, st, alpha, VsBwdArgs{});
+}
+
 // prbvolpath's single-pass backward on the phase scheduler: n samples of the
 // lane map, gradients into bw.ga's slot buffers (k_prbvol_backward's Mode 2)
-hipError_t launch_vol_sched_bwd(const DScene &S0, const IntegratorParams &in, const LaneMap &lm, uint32_t seed_value,
+hipError_t launch_vol_sched_bwd(const DScene &S, const IntegratorParams &in, const LaneMap &lm, uint32_t seed_value,
                                 uint64_t n, const VsBwdArgs &bw, uint32_t grid, unsigned long long *counters,
                                 hipStream_t st) {
     if (n == 0) return hipSuccess;
     if (in.type != MH_INTEGRATOR_PRBVOLPATH || !bw.main_log || !bw.nee_log || !bw.main_cap || !bw.nee_cap)
         return hipErrorInvalidValue;
-    const bool pk = vol_packet(S0), tab = vs_tables(S0);
-    DScene S;
-    const bool blend = S0.vol_flags & kVolPhaseBlend;
-    hipError_t e = bw.ga.emitter_off
-                       ? (blend ? vs_launch_scene<PvBwdMachineEmBlend>(S0, pk, tab, S) : vs_launch_scene<PvBwdMachineEm>(S0, pk, tab, S))
-                       : (blend ? vs_launch_scene<PvBwdMachineBlend>(S0, pk, tab, S) : vs_launch_scene<PvBwdMachine>(S0, pk, tab, S));
-    if (e != hipSuccess) return e;
-    const size_t sh = lds_bytes(S, 256);
-    const bool lds = S.lds_bytes_bvh != 0;
-    unsigned long long *work = counters + 32;  // the 8 queue heads of this launch (128 B apart)
-    e = hipMemsetAsync(work, 0, 8 * 128, st);
-    if (e != hipSuccess) return e;
-#define MH_VSB1(M, L, P, T)                                                                                    \
-    hipLaunchKernelGGL((k_vol_sched<M, L, P, T>), dim3(grid), dim3(256), sh + (T ? vs_tab_bytes(S) : 0u) + (P ? vs_defer_bytes(S) : 0u), \
-                       st, S, in, lm, seed_value, n, (uint64_t)0, (float *)nullptr, counters, work, 0, bw)
-#define MH_VSB(L, P, T)                                                                                        \
-    do {                                                                                                       \
-        if (bw.ga.emitter_off && blend) MH_VSB1(PvBwdMachineEmBlend, L, P, T);                                 \
-        else if (bw.ga.emitter_off) MH_VSB1(PvBwdMachineEm, L, P, T);                                          \
-        else if (blend) MH_VSB1(PvBwdMachineBlend, L, P, T);                                                   \
-        else MH_VSB1(PvBwdMachine, L, P, T);                                                                   \
-    } while (0)
-    if (pk && tab) MH_VSB(false, true, true);
-    else if (pk) MH_VSB(false, true, false);
-    else if (lds) MH_VSB(true, false, false);
-    else MH_VSB(false, false, false);
-#undef MH_VSB
-#undef MH_VSB1
-    return hipGetLastError();
+    return vs_launch(variant::vol_sched_bwd(variant_facts(S), bw.ga.emitter_off != 0), S, in, lm, seed_value, n,
+                     (uint64_t)0, (float *)nullptr, grid, counters, st, 0, bw);
 }
 
 // A path whose MainLog overflowed: its adjoint replayed with L = its radiance
@@ -2124,16 +2079,11 @@ hipError_t launch_vol_sched_bwd_replays(const DScene &S, const IntegratorParams 
     // the lists' lengths stay on the device: every thread beyond them leaves at once
     const size_t sh = lds_bytes(S, 256);
     const uint32_t gp = (bw.ovf_cap + 255) / 256, gw = gp;
-    const bool blend = S.vol_flags & kVolPhaseBlend;  // the paths' replay samples phase functions; the walks' does not
-    if (S.lds_bytes_bvh) {
-        if (blend) hipLaunchKernelGGL((k_pvb_replay_paths<true, kPhBlend>), dim3(gp), dim3(256), sh, st, S, in, lm, seed_value, bw, counters);
-        else hipLaunchKernelGGL((k_pvb_replay_paths<true>), dim3(gp), dim3(256), sh, st, S, in, lm, seed_value, bw, counters);
-        hipLaunchKernelGGL(k_pvb_replay_walks<true>, dim3(gw), dim3(256), sh, st, S, bw, counters);
-    } else {
-        if (blend) hipLaunchKernelGGL((k_pvb_replay_paths<false, kPhBlend>), dim3(gp), dim3(256), sh, st, S, in, lm, seed_value, bw, counters);
-        else hipLaunchKernelGGL((k_pvb_replay_paths<false>), dim3(gp), dim3(256), sh, st, S, in, lm, seed_value, bw, counters);
-        hipLaunchKernelGGL(k_pvb_replay_walks<false>, dim3(gw), dim3(256), sh, st, S, bw, counters);
-    }
+    // (the paths' replay samples phase functions; the walks' does not)
+    variant::dispatch(variant::vol_lane(variant_facts(S)), [&](auto, auto Ph, auto L, auto, auto) {
+        hipLaunchKernelGGL((k_pvb_replay_paths<L, Ph>), dim3(gp), dim3(256), sh, st, S, in, lm, seed_value, bw, counters);
+        hipLaunchKernelGGL(k_pvb_replay_walks<L>, dim3(gw), dim3(256), sh, st, S, bw, counters);
+    });
     return hipGetLastError();
 }
 
@@ -2154,52 +2104,26 @@ hipError_t launch_volwave(const DScene &S, const IntegratorParams &in, const Lan
     }
     const uint32_t seg_cap = (uint32_t)((n + kVwSeg - 1) / kVwSeg);
     const size_t sh = lds_bytes(S, 256);
-    const bool lds = S.lds_bytes_bvh != 0;
-    const bool pk = vol_packet(S);
-    const bool blend = S.vol_flags & kVolPhaseBlend;  // the kernels compiled with blendphase
+    const variant::Facts F = variant_facts(S);
     // main / walk rounds while many paths are live, then one finish launch
     const uint32_t wave_rounds = (uint32_t)env::vw_rounds((int)kVwWaveRounds);
     for (uint32_t r = 0; r < rounds; ++r) {
         const VwPlanes &c = side[r & 1], &x = side[(r + 1) & 1];
         const uint32_t *cin = ctr + (size_t)kVwCtr * r;
         uint32_t *cout = ctr + (size_t)kVwCtr * (r + 1);
+        const variant::VolKernel key = variant::volwave(F, r == 0);
         if (r == wave_rounds) {
-#define MH_VW_FIN(L, P)                                                                                             \
-    do {                                                                                                            \
-        if (blend) hipLaunchKernelGGL((k_vw_finish<L, P, kPhBlend>), dim3(grid), dim3(256), sh, st, S, in, plane, out, c, seg_cap, cin, counters, alpha); \
-        else hipLaunchKernelGGL((k_vw_finish<L, P>), dim3(grid), dim3(256), sh, st, S, in, plane, out, c, seg_cap, cin, counters, alpha);                \
-    } while (0)
-            if (pk) MH_VW_FIN(false, true);
-            else if (lds) MH_VW_FIN(true, false);
-            else MH_VW_FIN(false, false);
-#undef MH_VW_FIN
+            variant::dispatch(key, [&](auto, auto Ph, auto L, auto P, auto) {
+                hipLaunchKernelGGL((k_vw_finish<L, P, Ph>), dim3(grid), dim3(256), sh, st, S, in, plane, out, c, seg_cap, cin, counters, alpha);
+            });
             break;
         }
-#define MH_VW_MAIN(F, L, P)                                                                                   \
-    do {                                                                                                      \
-        if (blend) hipLaunchKernelGGL((k_vw_main<F, L, P, kPhBlend>), dim3(grid), dim3(256), sh, st, S, in, lm, seed_value, n, plane, out, \
-                                      c, x, seg_cap, cin, cout, counters, alpha);                             \
-        else hipLaunchKernelGGL((k_vw_main<F, L, P>), dim3(grid), dim3(256), sh, st, S, in, lm, seed_value, n, plane, out, \
-                                c, x, seg_cap, cin, cout, counters, alpha);                                   \
-    } while (0)
-#define MH_VW_WALK(L, P) \
-    hipLaunchKernelGGL((k_vw_walk<L, P>), dim3(grid), dim3(256), sh, st, S, x, seg_cap, cout, counters)
-        if (pk) {
-            if (r == 0) MH_VW_MAIN(true, false, true);
-            else MH_VW_MAIN(false, false, true);
-        } else if (r == 0) {
-            if (lds) MH_VW_MAIN(true, true, false);
-            else MH_VW_MAIN(true, false, false);
-        } else {
-            if (lds) MH_VW_MAIN(false, true, false);
-            else MH_VW_MAIN(false, false, false);
-        }
-        if (r + 1 == rounds) break;  // depth < max_depth: no walk after the last round
-        if (pk) MH_VW_WALK(false, true);
-        else if (lds) MH_VW_WALK(true, false);
-        else MH_VW_WALK(false, false);
-#undef MH_VW_MAIN
-#undef MH_VW_WALK
+        variant::dispatch(key, [&](auto Fresh, auto Ph, auto L, auto P, auto) {
+            hipLaunchKernelGGL((k_vw_main<Fresh, L, P, Ph>), dim3(grid), dim3(256), sh, st, S, in, lm, seed_value, n, plane, out,
+                               c, x, seg_cap, cin, cout, counters, alpha);
+            if (r + 1 == rounds) return;  // depth < max_depth: no walk after the last round
+            hipLaunchKernelGGL((k_vw_walk<L, P>), dim3(grid), dim3(256), sh, st, S, x, seg_cap, cout, counters);
+        });
     }
     return hipGetLastError();
 }

@@ -82,40 +82,15 @@ uint32_t wf_packet_max_prims() {
     static const uint32_t v = (uint32_t)env::packet_max_prims((int)kPacketMaxPrims);
     return v;
 }
-static bool use_packet(const DScene &S) {
-    if (S.n_prims > wf_packet_max_prims()) return false;  // no pair records beyond (mh_api.hip)
-    return !env::traversal_lane();
+variant::Facts variant_facts(const DScene &S) {
+    // (no pair records beyond wf_packet_max_prims(): mh_api.hip; MH_WF_FUSED=0 keeps the three-kernel pipeline)
+    return {S.lds_bytes_bvh != 0, S.n_prims, wf_packet_max_prims(), S.tab_bytes != 0, S.vol_flags, stream_engine(S),
+            env::traversal_lane(), env::vs_notab(), env::wf_unfused()};
 }
-// MH_WF_FUSED=0 keeps the three-kernel pipeline (trace / shade / shadow)
-static bool wf_unfused() { return env::wf_unfused(); }
-// the stream kernels are instantiated per node format (Eng), so each one's
-// register allocation is that of its own traversal engine
-#define MH_WF_DISPATCH(K, ...)                                                                        \
-    do {                                                                                              \
-        const dim3 g_(grid), b_(256);                                                                 \
-        if (lds && packet) hipLaunchKernelGGL((K<true, true, kEngBvh2>), g_, b_, sh, st, __VA_ARGS__);         \
-        else if (lds) hipLaunchKernelGGL((K<true, false, kEngBvh2>), g_, b_, sh, st, __VA_ARGS__);           \
-        else if (packet) hipLaunchKernelGGL((K<false, true, kEngBvh2>), g_, b_, sh, st, __VA_ARGS__);        \
-        else switch (stream_engine(S)) {                                                              \
-            case kEngQuant: hipLaunchKernelGGL((K<false, false, kEngQuant>), g_, b_, sh, st, __VA_ARGS__); break; \
-            case kEngWideC: hipLaunchKernelGGL((K<false, false, kEngWideC>), g_, b_, sh, st, __VA_ARGS__); break; \
-            case kEngWide: hipLaunchKernelGGL((K<false, false, kEngWide>), g_, b_, sh, st, __VA_ARGS__); break;   \
-            default: hipLaunchKernelGGL((K<false, false, kEngBvh2>), g_, b_, sh, st, __VA_ARGS__); break;        \
-        }                                                                                             \
-    } while (0)
-#define MH_WF_DISPATCH_NR(K, NR, ...)                                                                 \
-    do {                                                                                              \
-        const dim3 g_(grid), b_(256);                                                                 \
-        if (lds && packet) hipLaunchKernelGGL((K<true, true, NR, kEngBvh2>), g_, b_, sh, st, __VA_ARGS__);     \
-        else if (lds) hipLaunchKernelGGL((K<true, false, NR, kEngBvh2>), g_, b_, sh, st, __VA_ARGS__);       \
-        else if (packet) hipLaunchKernelGGL((K<false, true, NR, kEngBvh2>), g_, b_, sh, st, __VA_ARGS__);    \
-        else switch (stream_engine(S)) {                                                              \
-            case kEngQuant: hipLaunchKernelGGL((K<false, false, NR, kEngQuant>), g_, b_, sh, st, __VA_ARGS__); break; \
-            case kEngWideC: hipLaunchKernelGGL((K<false, false, NR, kEngWideC>), g_, b_, sh, st, __VA_ARGS__); break; \
-            case kEngWide: hipLaunchKernelGGL((K<false, false, NR, kEngWide>), g_, b_, sh, st, __VA_ARGS__); break;   \
-            default: hipLaunchKernelGGL((K<false, false, NR, kEngBvh2>), g_, b_, sh, st, __VA_ARGS__); break;        \
-        }                                                                                             \
-    } while (0)
+static_assert(variant::kPhExt == kPhExt && variant::kPhBlend == kPhBlend &&
+              variant::kEngBvh2 == kEngBvh2 && variant::kEngWide == kEngWide && variant::kEngQuant == kEngQuant &&
+              variant::kEngWideC == kEngWideC && variant::kVolPhaseExt == kVolPhaseExt &&
+              variant::kVolPhaseBlend == kVolPhaseBlend, "mh_variant.hpp names the kernels' values");
 
 static inline size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
 
@@ -775,13 +750,14 @@ static hipError_t launch_wavefront_pass(const DScene &S, const IntegratorParams 
                                         uint64_t cap, uint32_t *ctr, uint32_t n_bounces, uint32_t grid,
                                         hipEvent_t *trace_ev, hipStream_t st, uint64_t *carry, uint32_t pass,
                                         int alpha) {
-    const bool fused = wf_fused(S);
+    const variant::Facts F = variant_facts(S);
+    const bool fused = variant::wf_fused(F);
+    const variant::WfTrace trav = variant::wf_trace(F);
     WfState w = carve(ws, cap);
     const WfPacked pk = carve_packed(ws, nullptr, cap);
     hipError_t e = hipMemsetAsync(ctr, 0, sizeof(uint32_t) * kCtrStride * (n_bounces + 1), st);
     if (e != hipSuccess) return e;
-    const bool lds = S.lds_bytes_bvh != 0, packet = use_packet(S);
-    const size_t sh = packet ? lds_bytes(S, 256) : stream_lds_bytes(S, 256);
+    const size_t sh = trav.packet ? lds_bytes(S, 256) : stream_lds_bytes(S, 256);
     const uint32_t seg_cap = seg_len(n);
     grid = std::max<uint32_t>(kSeg, grid / kSeg * kSeg);  // whole number of blocks per segment
     if (S.stack_ovf && (uint64_t)grid * 256 > S.ovf_threads) return hipErrorInvalidValue;  // overflow columns
@@ -799,25 +775,25 @@ static hipError_t launch_wavefront_pass(const DScene &S, const IntegratorParams 
             // after it, ~75 us of idle GPU per chunk)
             if (trace_ev && b == 0) (void)hipEventRecord(trace_ev[0], st);
             const uint32_t gd = grid;
-            if (b == 0)
-                hipLaunchKernelGGL(k_wf_bounce<true>, dim3(gd), dim3(256), fused_lds_bytes(S), st, S,
+            variant::select([&](auto Gen) {
+                hipLaunchKernelGGL(k_wf_bounce<Gen>, dim3(gd), dim3(256), fused_lds_bytes(S), st, S,
                                    in, lm, seed_value, plane, out, pk, cur, seg_cap, c, cn, n, carry, pass, alpha);
-            else
-                hipLaunchKernelGGL(k_wf_bounce<false>, dim3(gd), dim3(256), fused_lds_bytes(S), st,
-                                   S, in, lm, seed_value, plane, out, pk, cur, seg_cap, c, cn, n, carry, pass, alpha);
+            }, variant::flag(b == 0));
             if (trace_ev && b + 1 == n_bounces) (void)hipEventRecord(trace_ev[1], st);
             continue;
         }
         if (trace_ev) (void)hipEventRecord(trace_ev[2 * b], st);
-        MH_WF_DISPATCH(k_wf_trace, S, w, cur, seg_cap, c);
+        variant::dispatch(trav, [&](auto L, auto P, auto Eng, auto) {
+            hipLaunchKernelGGL((k_wf_trace<L, P, Eng>), dim3(grid), dim3(256), sh, st, S, w, cur, seg_cap, c);
+        });
         if (trace_ev) (void)hipEventRecord(trace_ev[2 * b + 1], st);
-        if (S.tab_bytes)
-            hipLaunchKernelGGL(k_wf_shade<true>, dim3(grid), dim3(256), S.tab_bytes, st, S, in, lm, seed_value,
+        variant::select([&](auto STAGED) {
+            hipLaunchKernelGGL(k_wf_shade<STAGED>, dim3(grid), dim3(256), STAGED ? S.tab_bytes : 0, st, S, in, lm, seed_value,
                                plane, out, w, cur, seg_cap, c, cn, alpha);
-        else
-            hipLaunchKernelGGL(k_wf_shade<false>, dim3(grid), dim3(256), 0, st, S, in, lm, seed_value, plane, out,
-                               w, cur, seg_cap, c, cn, alpha);
-        MH_WF_DISPATCH(k_wf_shadow, S, w, plane, out, seg_cap, c);
+        }, variant::flag(F.tables));
+        variant::dispatch(trav, [&](auto L, auto P, auto Eng, auto) {
+            hipLaunchKernelGGL((k_wf_shadow<L, P, Eng>), dim3(grid), dim3(256), sh, st, S, w, plane, out, seg_cap, c);
+        });
     }
     return hipGetLastError();
 }
@@ -1849,17 +1825,10 @@ hipError_t launch_wavefront_fwd(const DScene &S, const IntegratorParams &in, con
     for (uint32_t b = 0; b < n_bounces; ++b) {
         uint32_t *c = ctr + kCtrStride * b, *cn = ctr + kCtrStride * (b + 1);
         const int cur = (int)(b & 1);
-#define MH_BOUNCE_FWD(GEN, EM)                                                                                  \
-    hipLaunchKernelGGL((k_wf_bounce_fwd<GEN, EM>), dim3(grid), dim3(256), sh_fused, st, S, in, lm, seed_value, w, q, \
-                       cur, seg_cap, c, cn, n, fo)
-        if (emitter_off) {
-            if (b == 0) MH_BOUNCE_FWD(true, true);
-            else MH_BOUNCE_FWD(false, true);
-        } else {
-            if (b == 0) MH_BOUNCE_FWD(true, false);
-            else MH_BOUNCE_FWD(false, false);
-        }
-#undef MH_BOUNCE_FWD
+        variant::select([&](auto Gen, auto Em) {
+            hipLaunchKernelGGL((k_wf_bounce_fwd<Gen, Em>), dim3(grid), dim3(256), sh_fused, st, S, in, lm, seed_value, w, q,
+                               cur, seg_cap, c, cn, n, fo);
+        }, variant::flag(b == 0), variant::flag(emitter_off != 0));
     }
     return hipGetLastError();
 }
@@ -2134,10 +2103,11 @@ hipError_t launch_wavefront_prb(const DScene &S, const IntegratorParams &in, con
     const bool em = emitter_off != 0;  // selects the Em instances; a call without an emitter parameter launches the others
     hipError_t e = hipMemsetAsync(ctr, 0, sizeof(uint32_t) * kCtrStride * (n_bounces + 1), st);
     if (e != hipSuccess) return e;
-    const bool lds = S.lds_bytes_bvh != 0, packet = use_packet(S);
-    const size_t sh = packet ? lds_bytes(S, 256) : stream_lds_bytes(S, 256);
+    const variant::Facts F = variant_facts(S);
+    const variant::WfTrace trav = variant::wf_trace(F, n_rgb);
+    const size_t sh = trav.packet ? lds_bytes(S, 256) : stream_lds_bytes(S, 256);
     const uint32_t seg_cap = seg_len(n);
-    const bool fused = packet && S.tab_bytes != 0 && !wf_unfused();
+    const bool fused = variant::wf_fused(F);
     const size_t sh_fused = fused_lds_bytes(S);
     if (S.stack_ovf && (uint64_t)grid * 256 > S.ovf_threads) return hipErrorInvalidValue;  // overflow columns
     const bool with_bmp = bmp != nullptr;
@@ -2158,82 +2128,32 @@ hipError_t launch_wavefront_prb(const DScene &S, const IntegratorParams &in, con
 #ifdef MH_EXP_BPHASE
     g_prb_ring_lds = sh_fused + (prb_nee_ring<1, false, false, false>() ? 4u * kNeeRingFloats * 4u : 0u);
 #endif
-#define MH_BOUNCE_PRB(NR, GEN, BM, DET, EM)                                                                    \
-    hipLaunchKernelGGL((k_wf_bounce_prb<NR, GEN, BM, DET, EM>),                                                \
-                       dim3(grid), dim3(256),      \
-                       sh_fused + (prb_nee_ring<NR, GEN, BM, DET>() ? 4u * kNeeRingFloats * 4u : 0u), st, S, in, lm, seed_value, w, q, cur, seg_cap, c, cn, gen, bm, det)
-#define MH_BOUNCE_PRB_NR(GEN, BM, DET)                                                                         \
-    do {                                                                                                       \
-        if (em) {                                                                                              \
-            if (n_rgb <= 1) MH_BOUNCE_PRB(1, GEN, BM, DET, true);                                              \
-            else MH_BOUNCE_PRB(kMaxRgbParams, GEN, BM, DET, true);                                             \
-        } else {                                                                                               \
-            if (n_rgb <= 1) MH_BOUNCE_PRB(1, GEN, BM, DET, false);                                             \
-            else MH_BOUNCE_PRB(kMaxRgbParams, GEN, BM, DET, false);                                            \
-        }                                                                                                      \
-    } while (0)
     for (uint32_t b = 0; b < n_bounces; ++b) {
         uint32_t *c = ctr + kCtrStride * b, *cn = ctr + kCtrStride * (b + 1);
         const int cur = (int)(b & 1);
         if (fused) {
-            if (with_bmp && det_on) {
-                if (b == 0) MH_BOUNCE_PRB_NR(true, true, true);
-                else MH_BOUNCE_PRB_NR(false, true, true);
-            } else if (with_bmp) {
-                if (b == 0) MH_BOUNCE_PRB_NR(true, true, false);
-                else MH_BOUNCE_PRB_NR(false, true, false);
-            } else if (det_on) {
-                if (b == 0) MH_BOUNCE_PRB_NR(true, false, true);
-                else MH_BOUNCE_PRB_NR(false, false, true);
-            } else {
-                if (b == 0) MH_BOUNCE_PRB_NR(true, false, false);
-                else MH_BOUNCE_PRB_NR(false, false, false);
-            }
+            variant::bounce_prb(b == 0, n_rgb, with_bmp, det_on, em, [&](auto NR1, auto GEN, auto BM, auto DET, auto EM) {
+                constexpr int NR = NR1 ? 1 : kMaxRgbParams;
+                hipLaunchKernelGGL((k_wf_bounce_prb<NR, GEN, BM, DET, EM>), dim3(grid), dim3(256),
+                                   sh_fused + (prb_nee_ring<NR, GEN, BM, DET>() ? 4u * kNeeRingFloats * 4u : 0u), st, S, in, lm, seed_value, w, q, cur, seg_cap, c, cn, gen, bm, det);
+            });
             continue;
         }
-        MH_WF_DISPATCH(k_wf_trace, S, w, cur, seg_cap, c);
-#define MH_SHADE_PRB(STAGED, NR, EM)                                                                           \
-    hipLaunchKernelGGL((k_wf_shade_prb<STAGED, NR, EM>), dim3(grid), dim3(256), STAGED ? S.tab_bytes : 0, st, S, in, \
-                       lm, seed_value, w, q, cur, seg_cap, c, cn)
-#define MH_SHADE_PRB_EM(STAGED, NR)                                                                            \
-    do {                                                                                                       \
-        if (em) MH_SHADE_PRB(STAGED, NR, true);                                                                \
-        else MH_SHADE_PRB(STAGED, NR, false);                                                                  \
-    } while (0)
-        if (n_rgb == 1) {
-            if (S.tab_bytes) MH_SHADE_PRB_EM(true, 1);
-            else MH_SHADE_PRB_EM(false, 1);
-        } else {
-            if (S.tab_bytes) MH_SHADE_PRB_EM(true, kMaxRgbParams);
-            else MH_SHADE_PRB_EM(false, kMaxRgbParams);
-        }
-#undef MH_SHADE_PRB_EM
-#undef MH_SHADE_PRB
-        if (n_rgb == 1) MH_WF_DISPATCH_NR(k_wf_shadow_prb, 1, S, w, q, seg_cap, c);
-        else MH_WF_DISPATCH_NR(k_wf_shadow_prb, kMaxRgbParams, S, w, q, seg_cap, c);
+        variant::dispatch(trav, [&](auto L, auto P, auto Eng, auto) {
+            hipLaunchKernelGGL((k_wf_trace<L, P, Eng>), dim3(grid), dim3(256), sh, st, S, w, cur, seg_cap, c);
+        });
+        variant::shade_prb(F, n_rgb, em, [&](auto STAGED, auto NR1, auto EM) {
+            hipLaunchKernelGGL((k_wf_shade_prb<STAGED, NR1 ? 1 : kMaxRgbParams, EM>), dim3(grid), dim3(256), STAGED ? S.tab_bytes : 0, st, S, in,
+                               lm, seed_value, w, q, cur, seg_cap, c, cn);
+        });
+        variant::dispatch(trav, [&](auto L, auto P, auto Eng, auto NR1) {
+            hipLaunchKernelGGL((k_wf_shadow_prb<L, P, NR1 ? 1 : kMaxRgbParams, Eng>), dim3(grid), dim3(256), sh, st, S, w, q, seg_cap, c);
+        });
     }
-#undef MH_BOUNCE_PRB_NR
-#undef MH_BOUNCE_PRB
     if (span) (void)hipEventRecord(span[1], st);  // the bounce span; span[1] -> span[2]: the scatter
     if (with_bmp) {
         const size_t acc_bytes = std::max<size_t>((size_t)bmp->n_floats * kScatAccBytes, 1);
         const bool in_lds = (size_t)bmp->n_floats * 4 <= bmp->lds_max && acc_bytes <= bmp->wg_lds;
-        // accumulators per CU: as many as its LDS holds, at most the workgroups
-        // of kScatThreads that are resident at once (more would only zero and
-        // flush extra LDS copies)
-        // (a thread-safe one-time query: calls on distinct scenes may run concurrently)
-        static const int resident = [] {
-            int r = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&r, k_wf_bitmap_scatter<true>, kScatThreads, 0) !=
-                hipSuccess) {
-                (void)hipGetLastError();
-                r = 0;
-            }
-            return r;
-        }();
-        const uint32_t per_cu = (uint32_t)std::max<size_t>(
-            1, std::min<size_t>(resident > 0 ? (size_t)resident : 8u, std::min<size_t>(8, bmp->cu_lds / acc_bytes)));
-        const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>(bmp->cus * per_cu, (uint32_t)((n + 4095) / 4096)));
         WfBmpTex bt;
         for (int b = 0; b < kMaxBitmapParams; ++b) { bt.tex[b] = bmp->tex[b]; bt.off[b] = bmp->off[b]; }
         bt.acc64 = bmp->fx_acc;
@@ -2241,11 +2161,40 @@ hipError_t launch_wavefront_prb(const DScene &S, const IntegratorParams &in, con
         bt.scale = 0.0;
         bt.n_rec = bmp->n_rec;
         const dim3 g_all((uint32_t)((n + 4095) / 4096));
-        if (bmp->fx_acc) {  // deterministic: max pass, then int64 pass, then fold (this chunk's own scale)
+        const bool fx = bmp->fx_acc != nullptr;
+        const auto scatter = [&](int fx_pass) {
+            variant::bitmap_scatter(fx, fx_pass, in_lds, [&](auto in_lds_c, auto fx_c) {
+                constexpr bool InLds = decltype(in_lds_c)::value;
+                constexpr int Fx = decltype(fx_c)::value;
+                if constexpr (InLds) {
+                    // accumulators per CU: as many as its LDS holds, at most the workgroups
+                    // of kScatThreads that are resident at once (more would only zero and
+                    // flush extra LDS copies)
+                    // (a thread-safe one-time query: calls on distinct scenes may run concurrently)
+                    static const int resident = [] {
+                        int r = 0;
+                        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&r, k_wf_bitmap_scatter<InLds, Fx>, kScatThreads, 0) !=
+                            hipSuccess) {
+                            (void)hipGetLastError();
+                            r = 0;
+                        }
+                        return r;
+                    }();
+                    const uint32_t per_cu = (uint32_t)std::max<size_t>(
+                        1, std::min<size_t>(resident > 0 ? (size_t)resident : 8u, std::min<size_t>(8, bmp->cu_lds / acc_bytes)));
+                    const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>(bmp->cus * per_cu, (uint32_t)((n + 4095) / 4096)));
+                    hipLaunchKernelGGL((k_wf_bitmap_scatter<InLds, Fx>), dim3(blocks), dim3(kScatThreads), (size_t)bmp->n_floats * kScatAccBytes, st, S,
+                                       bt, bm, (uint32_t)n, bmp->grad, bmp->n_floats);
+                } else {
+                    hipLaunchKernelGGL((k_wf_bitmap_scatter<InLds, Fx>), g_all, dim3(256), 0, st, S, bt, bm, (uint32_t)n,
+                                       bmp->grad, bmp->n_floats);
+                }
+            });
+        };
+        if (fx) {  // deterministic: max pass, then int64 pass, then fold (this chunk's own scale)
             e = hipMemsetAsync(bmp->fx_word, 0, 4, st);
             if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((k_wf_bitmap_scatter<false, 1>), g_all, dim3(256), 0, st, S, bt, bm, (uint32_t)n,
-                               bmp->grad, bmp->n_floats);
+            scatter(1);
             uint32_t mb = 0;
             e = hipMemcpyAsync(&mb, bmp->fx_word, 4, hipMemcpyDeviceToHost, st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -2257,17 +2206,12 @@ hipError_t launch_wavefront_prb(const DScene &S, const IntegratorParams &in, con
             bt.scale = std::ldexp(1.0, 31 - ex);
             e = hipMemsetAsync(bmp->fx_acc, 0, (size_t)bmp->n_floats * 8, st);
             if (e != hipSuccess) return e;
-            hipLaunchKernelGGL((k_wf_bitmap_scatter<false, 2>), g_all, dim3(256), 0, st, S, bt, bm, (uint32_t)n,
-                               bmp->grad, bmp->n_floats);
+            scatter(2);
             hipLaunchKernelGGL(k_fx_fold, dim3(std::max<uint32_t>(1, std::min<uint32_t>(4096, (bmp->n_floats + 255) / 256))),
                                dim3(256), 0, st, reinterpret_cast<const long long *>(bmp->fx_acc), bmp->grad,
                                bmp->n_floats, std::ldexp(1.0, ex - 31));
-        } else if (in_lds)
-            hipLaunchKernelGGL(k_wf_bitmap_scatter<true>, dim3(blocks), dim3(kScatThreads), (size_t)bmp->n_floats * kScatAccBytes, st, S,
-                               bt, bm, (uint32_t)n, bmp->grad, bmp->n_floats);
-        else
-            hipLaunchKernelGGL(k_wf_bitmap_scatter<false>, dim3((uint32_t)((n + 4095) / 4096)), dim3(256), 0, st, S,
-                               bt, bm, (uint32_t)n, bmp->grad, bmp->n_floats);
+        } else
+            scatter(0);
     }
     if (span) (void)hipEventRecord(span[2], st);
     if (det_on) {
@@ -2277,7 +2221,7 @@ hipError_t launch_wavefront_prb(const DScene &S, const IntegratorParams &in, con
     return hipGetLastError();
 }
 
-bool wf_fused(const DScene &S) { return use_packet(S) && S.tab_bytes != 0 && !wf_unfused(); }
+bool wf_fused(const DScene &S) { return variant::wf_fused(variant_facts(S)); }
 
 uint32_t wf_grid(uint32_t grid) { return std::max<uint32_t>(kSeg, grid / kSeg * kSeg); }
 // Workgroups of the wavefront kernels.  A wave's share of a queue is fixed
