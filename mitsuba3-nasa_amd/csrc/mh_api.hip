@@ -1329,7 +1329,7 @@ static int render_impl(mh_scene *s, const mh_integrator *in, uint32_t seed, uint
     const plan::RenderPlan plan = plan::plan_render(facts, env::plan_env(env::Call::Render));
     if (plan.err)
         return set_error(plan.err, "mh_render: the wavefront mode supports the 'path' integrator "
-                                   "with max_depth <= 64 (several passes: packet-engine scenes) and "
+                                   "with 1 <= max_depth <= 64 (several passes: packet-engine scenes) and "
                                    "'volpath' with max_depth <= 1024 (one pass)");
     const bool wavefront = plan.wavefront, volwave = plan.volwave, sched = plan.sched;
     const bool vw_debug = env::vw_debug();
@@ -1549,8 +1549,8 @@ int mh_render_samples(mh_scene *s, const mh_integrator *in, uint32_t seed, uint3
                               s->wf_ctr.as<uint32_t>(), vw_blocks(device_cus(s->device)),
                               s->counters.as<unsigned long long>(), st, alpha));
     } else if (flags & MH_FLAG_WAVEFRONT) {
-        if (in->type != MH_INTEGRATOR_PATH || in->max_depth > 64)
-            return set_error(MH_ERR_UNSUPPORTED, "mh_render_samples: wavefront mode needs 'path' (max_depth <= 64) "
+        if (in->type != MH_INTEGRATOR_PATH || in->max_depth == 0 || in->max_depth > 64)
+            return set_error(MH_ERR_UNSUPPORTED, "mh_render_samples: wavefront mode needs 'path' (1 <= max_depth <= 64) "
                                                  "or 'volpath' (max_depth <= 1024)");
         MH_HIP(s->wf_ws.alloc(wf_workspace_bytes(n)));
         MH_HIP(s->wf_ctr.alloc(std::max<size_t>(16, 4 * (size_t)wf_counter_words(in->max_depth))));

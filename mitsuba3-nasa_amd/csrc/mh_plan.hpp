@@ -104,8 +104,11 @@ struct RenderPlan {
 inline RenderPlan plan_render(const Facts &f, const PlanEnv &e) {
     RenderPlan p;
     // `path` of bounded depth; several passes only on the fused bounce kernel,
-    // which carries each lane's PCG32 state from one pass to the next.  volpath: single pass
-    p.wavefront = f.type == MH_INTEGRATOR_PATH && f.max_depth <= 64 && (f.n_passes == 1 || f.wf_fused);
+    // which carries each lane's PCG32 state from one pass to the next.  volpath: single pass.
+    // max_depth 0 launches no bounce kernel, and the fused wavefront's first
+    // bounce is what writes a sample's position: the per-lane kernel takes it
+    p.wavefront = f.type == MH_INTEGRATOR_PATH && f.max_depth >= 1 && f.max_depth <= 64 &&
+                  (f.n_passes == 1 || f.wf_fused);
     p.volwave = (f.vol_sched ? f.vs_ok : f.vw_ok) && f.n_passes == 1;
     if (megakernel(f.flags, e)) p.wavefront = p.volwave = false;
     if ((f.flags & MH_FLAG_WAVEFRONT) && !p.wavefront && !p.volwave) p.err = MH_ERR_UNSUPPORTED;
@@ -153,7 +156,9 @@ inline BackwardPlan plan_backward(const Facts &f, const PlanEnv &e) {
     // count (as the scatter's transposed issue assumes); MH_PRB_BMP_WF=0: replay
     p.bmp_wf = !vol && f.n_bmp >= 1 && f.bmp_same_ch && !p.replay && !p.mega && f.wf_fused && f.max_depth >= 1 &&
                f.max_depth <= 32 && !e.prb_bmp_wf_off;
-    p.wavefront = (p.fused && f.max_depth <= 64 && !p.mega) || p.bmp_wf;
+    // max_depth 0: prb still adds the emitter its camera ray sees (prb.py:121-135), whose
+    // radiance may be differentiated; the wavefront would launch no bounce kernel at all
+    p.wavefront = (p.fused && f.max_depth >= 1 && f.max_depth <= 64 && !p.mega) || p.bmp_wf;
     p.det_replay = p.determ && !vol && !p.wavefront;
     p.fxr = p.fx || p.det_replay;
     // one bitmap parameter of <= 48 KiB (det_replay switches it off again: no LDS accumulator there)

@@ -1665,7 +1665,10 @@ MH_DEV void wave_count(unsigned long long *ctr, uint32_t v) {
 // ===========================================================================
 MH_DEV V3 path_sample(const DScene &S, const LdsBvh &B, const IntegratorParams &in, Pcg &rng,
                       RayT ray, uint32_t &n_closest, uint32_t &n_shadow, bool *valid_out = nullptr) {
-    if (in.max_depth == 0) return v3(0, 0, 0);
+    if (in.max_depth == 0) {  // { 0.f, false } (path.cpp:103-104)
+        if (valid_out) *valid_out = false;
+        return v3(0, 0, 0);
+    }
     V3 throughput = v3(1, 1, 1), result = v3(0, 0, 0);
     float eta = 1.f;
     uint32_t depth = 0;

@@ -98,6 +98,10 @@ def test_render_engine(cases):
     _sub(cases["render_prb_flag_wavefront"], err=4, engine="mega")        # MH_ERR_UNSUPPORTED
     _sub(cases["render_depth_64"], err=0, engine="wavefront", mode=2)
     _sub(cases["render_depth_65"], err=0, **mega)
+    # max_depth 0: no bounce kernel would run, and the first one writes the positions
+    _sub(cases["render_depth_0"], err=0, **mega)
+    _sub(cases["render_depth_0_flag_wavefront"], err=4, engine="mega")
+    _sub(cases["render_depth_1"], err=0, engine="wavefront", mode=2)
     _sub(cases["render_passes_fused"], engine="wavefront", mode=2, chunk_px=512, n_chunks=2, two=1)
     _sub(cases["render_passes_unfused"], **mega)
     _sub(cases["render_unfused"], engine="wavefront", mode=1, two=1)
@@ -117,6 +121,12 @@ def test_backward_engine(cases):
     _sub(cases["bwd_rgb_chunk_1024"], wavefront=1, max_samples=1024, chunk_px=128, n_chunks=2, two=1)
     _sub(cases["bwd_rgb_chunk_1024_one_stream"], wavefront=1, chunk_px=128, n_chunks=2, two=0)
     _sub(cases["bwd_rgb_mega"], fused=1, mega=1, wavefront=0, n_chunks=0)
+    # prb at max_depth 0 still sees the emitter (prb.py:121-135): the per-lane
+    # kernel, as above 64 -- the wavefront would launch no bounce kernel
+    _sub(cases["bwd_depth_0"], fused=1, mega=0, wavefront=0, n_chunks=0)
+    _sub(cases["bwd_depth_1"], fused=1, wavefront=1, n_chunks=1)
+    _sub(cases["bwd_depth_64"], fused=1, wavefront=1, n_chunks=1)
+    _sub(cases["bwd_depth_65"], fused=1, mega=0, wavefront=0, n_chunks=0)
     _sub(cases["bwd_bmp_depth_32"], fused=0, bmp_wf=1, wavefront=1)
     for name in ("bwd_bmp_depth_33", "bwd_bmp_mixed_channels", "bwd_bmp_unfused", "bwd_bmp_wf_off"):
         _sub(cases[name], fused=0, bmp_wf=0, wavefront=0, replay=0)  # the replay kernel, not forced

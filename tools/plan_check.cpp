@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <initializer_list>
+#include <string>
 #include <utility>
 
 #include "../mitsuba3-nasa_amd/csrc/mh_env.hpp"
@@ -106,6 +107,9 @@ int main() {
     render("render_mode_other", big, {{"MH_MODE", "megakernel"}});
     render("render_flag_megakernel", facts(PATH, 8, 32, 32, 512, MH_FLAG_MEGAKERNEL));
     render("render_prb_flag_wavefront", facts(PRB, 8, 32, 32, 512, MH_FLAG_WAVEFRONT));
+    render("render_depth_0", facts(PATH, 0, 32, 32, 512));
+    render("render_depth_0_flag_wavefront", facts(PATH, 0, 32, 32, 512, MH_FLAG_WAVEFRONT));
+    render("render_depth_1", facts(PATH, 1, 32, 32, 512));
     render("render_depth_64", facts(PATH, 64, 32, 32, 512));
     render("render_depth_65", facts(PATH, 65, 32, 32, 512));
     {
@@ -136,6 +140,11 @@ int main() {
     backward("bwd_rgb_chunk_1024", rgb, {{"MH_WF_CHUNK", "1024"}});
     backward("bwd_rgb_chunk_1024_one_stream", rgb, {{"MH_WF_CHUNK", "1024"}, {"MH_WF_STREAMS", "1"}});
     backward("bwd_rgb_mega", rgb, {{"MH_MODE", "mega"}});
+    for (uint32_t depth : {0u, 1u, 64u, 65u}) {
+        plan::Facts f = rgb;
+        f.max_depth = depth;
+        backward(("bwd_depth_" + std::to_string(depth)).c_str(), f);
+    }
     backward("bwd_bmp_depth_32", bmp);
     {
         plan::Facts f = bmp;
