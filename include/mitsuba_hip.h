@@ -15,7 +15,7 @@
  *       Scene::Scene + accel_init_gpu (OptiX GAS/IAS build)
  *       src/render/scene.cpp:22-96, src/render/scene_optix.inl:304-547
  *   mh_scene_update_texture / mh_scene_update_rgb / mh_scene_update_medium /
- *   mh_scene_update_emitter
+ *   mh_scene_update_medium_phase / mh_scene_update_emitter
  *       SceneParameters.update -> Scene::parameters_changed
  *       src/python/python/util.py:292-350, src/render/scene.cpp:481-529
  *   mh_render
@@ -104,11 +104,21 @@ enum { MH_INTEGRATOR_PATH = 0, MH_INTEGRATOR_VOLPATH = 1, MH_INTEGRATOR_PRB = 2,
  *   MH_PARAM_EMITTER_RADIANCE | e : mh_emitter::radiance of emitter e (3 floats):
  *                                 '<shape>.emitter.radiance.value' (area),
  *                                 '<name>.radiance.value' (constant) or
- *                                 '<name>.irradiance.value' (directional)    */
+ *                                 '<name>.irradiance.value' (directional)
+ *   MH_PARAM_MEDIUM_PHASE_G | m : '<medium>.phase_function.g' (1 float), the
+ *                                 Henyey-Greenstein asymmetry (hg.cpp:61-63)
+ *                                 of a medium whose phase is MH_PHASE_HG, with
+ *                                 MH_INTEGRATOR_PRBVOLPATH; on any other medium
+ *                                 or integrator the call fails with an error
+ *                                 code and a message and changes nothing.  The
+ *                                 parameters of the other phase functions
+ *                                 (tables, blend weights and children) are not
+ *                                 differentiable.                             */
 #define MH_PARAM_KIND_MASK      0xF0000000u
 #define MH_PARAM_MEDIUM_SIGMA_T 0x10000000u
 #define MH_PARAM_MEDIUM_ALBEDO  0x20000000u
 #define MH_PARAM_EMITTER_RADIANCE 0x30000000u
+#define MH_PARAM_MEDIUM_PHASE_G 0x40000000u
 
 /* Flags for mh_render / mh_render_backward / mh_trace_*                   */
 enum {
@@ -316,6 +326,11 @@ int mh_scene_update_rgb(mh_scene *scene, uint32_t texture, const float value[3])
  */
 int mh_scene_update_medium(mh_scene *scene, uint32_t medium, const float *albedo, const float *sigma_t,
                            const float *grid, uint64_t n, uint32_t flags);
+/* The asymmetry g of a medium whose phase function is MH_PHASE_HG
+ * ('<medium>.phase_function.g').  g must lie in (-1, 1); a value outside, a
+ * medium with another phase function or an index out of bounds is an error
+ * and leaves the scene, on the host and on the device, as it was. */
+int mh_scene_update_medium_phase(mh_scene *scene, uint32_t medium, float g);
 int mh_scene_update_texture(mh_scene *scene, uint32_t texture, const float *data, uint64_t n_floats);
 /* An emitter's radiance (area / constant) or irradiance (directional), 3
  * floats (host): traverse()/update() of '<shape>.emitter.radiance.value',
@@ -503,6 +518,14 @@ int mh_trace_shadow(mh_scene *scene, uint64_t n, const float *rays, uint32_t *oc
 int mh_phase_sample(mh_scene *scene, uint32_t medium, uint64_t n, const float *u, float *wo, float *pdf,
                     uint32_t flags);
 int mh_phase_eval(mh_scene *scene, uint32_t medium, uint64_t n, const float *wo, float *value, uint32_t flags);
+/* The derivative of mh_phase_eval's value with respect to the asymmetry g of
+ * an MH_PHASE_HG medium, d p / d g = p * (-2 g / (1 - g^2) - 3 (g + cos) / temp)
+ * with cos = -wo.z and temp = 1 + g^2 + 2 g cos: the device function the
+ * prbvolpath adjoint charges for MH_PARAM_MEDIUM_PHASE_G.  Layouts and flags
+ * as mh_phase_eval; a medium with another phase function is MH_ERR_UNSUPPORTED.
+ *   mh_phase_eval_grad : wo = SoA x[n] y[n] z[n] -> dvalue_dg[n]            */
+int mh_phase_eval_grad(mh_scene *scene, uint32_t medium, uint64_t n, const float *wo, float *dvalue_dg,
+                       uint32_t flags);
 /*
  * The same queries with PhaseFunction::sample's sample1 and the interaction
  * point, which a blend reads (the child selection; weight_0 at the point, looked

@@ -712,6 +712,27 @@ int mh_scene_update_medium(mh_scene *s, uint32_t medium, const float *albedo, co
     return MH_OK;
 }
 
+// SceneParameters.update of an `hg` medium's asymmetry (hg.cpp:61-63, and its
+// constructor's range check): the host description, the host image of the
+// device record and the device record itself.  Nothing changes on an error.
+int mh_scene_update_medium_phase(mh_scene *s, uint32_t medium, float g) {
+    if (!s) return set_error(MH_ERR_INVALID_ARGUMENT, "mh_scene_update_medium_phase: NULL scene");
+    if (medium >= s->n_media)
+        return set_error(MH_ERR_INVALID_ARGUMENT, "mh_scene_update_medium_phase: medium index out of bounds");
+    if (s->h_dmedia[medium].phase != MH_PHASE_HG)
+        return set_error(MH_ERR_INVALID_ARGUMENT, "mh_scene_update_medium_phase: the medium's phase function is not MH_PHASE_HG");
+    if (!(g > -1.f && g < 1.f))
+        return set_error(MH_ERR_INVALID_ARGUMENT, "The asymmetry parameter must lie in the interval (-1, 1)!");
+    MH_HIP(hipSetDevice(s->device));
+    DMedium b = s->h_dmedia[medium];
+    b.g = g;
+    MH_HIP(hipMemcpyAsync(s->media.as<DMedium>() + medium, &b, sizeof(DMedium), hipMemcpyHostToDevice, s->stream));
+    MH_HIP(hipStreamSynchronize(s->stream));
+    s->h_media[medium].g = g;
+    s->h_dmedia[medium] = b;
+    return MH_OK;
+}
+
 // The table of a tabulated phase function: what IrregularContinuousDistribution
 // ::compute_cdf_scalar builds (distr_1d.h:916-978) -- the interval integrals
 // accumulated in double and stored as float, the first and last interval with
@@ -986,10 +1007,14 @@ static int check_phase_tables(const mh_scene *s, const char *fn) {
 
 // Phase-function queries: a grid-stride kernel around phase_sample / phase_eval.
 // at: the position-aware calls (sample: in = u1 u2x u2y, pos = the interaction points)
+// grad: mh_phase_eval_grad, the evaluation's derivative with respect to an `hg` medium's g
 static int phase_query(mh_scene *s, const char *fn, bool sample, bool at, uint32_t medium, uint64_t n, const float *in,
-                       const float *pos, float *out, float *pdf, uint32_t flags) {
+                       const float *pos, float *out, float *pdf, uint32_t flags, bool grad = false) {
     if (!s) return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + ": NULL scene");
     if (medium >= s->n_media) return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + ": medium index out of bounds");
+    if (grad && s->h_dmedia[medium].phase != MH_PHASE_HG)
+        return set_error(MH_ERR_UNSUPPORTED, std::string(fn) + ": the medium's phase function is not MH_PHASE_HG (other "
+                                                               "phase functions' parameters are not differentiable)");
     if (n && (!in || !out || (sample && !pdf) || (at && !pos)))
         return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + ": NULL argument");
     if (n >= (1ull << 32)) return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + ": more than 2^32 - 1 items");
@@ -1019,7 +1044,8 @@ static int phase_query(mh_scene *s, const char *fn, bool sample, bool at, uint32
         d_pdf = d_out + n_out;
     }
     const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)device_cus(s->device) * 8);
-    MH_HIP(launch_phase_query(s->S, sample, medium, n, d_in, d_pos, d_out, d_pdf, grid, st));
+    if (grad) MH_HIP(launch_phase_eval_grad(s->S, medium, n, d_in, d_out, grid, st));
+    else MH_HIP(launch_phase_query(s->S, sample, medium, n, d_in, d_pos, d_out, d_pdf, grid, st));
     if (!dev) {
         MH_HIP(hipMemcpyAsync(out, d_out, n_out * 4, hipMemcpyDeviceToHost, st));
         if (sample) MH_HIP(hipMemcpyAsync(pdf, d_pdf, n * 4, hipMemcpyDeviceToHost, st));
@@ -1032,6 +1058,9 @@ int mh_phase_sample(mh_scene *s, uint32_t medium, uint64_t n, const float *u, fl
 }
 int mh_phase_eval(mh_scene *s, uint32_t medium, uint64_t n, const float *wo, float *value, uint32_t flags) {
     return phase_query(s, "mh_phase_eval", false, false, medium, n, wo, nullptr, value, nullptr, flags);
+}
+int mh_phase_eval_grad(mh_scene *s, uint32_t medium, uint64_t n, const float *wo, float *dvalue_dg, uint32_t flags) {
+    return phase_query(s, "mh_phase_eval_grad", false, false, medium, n, wo, nullptr, dvalue_dg, nullptr, flags, true);
 }
 int mh_phase_sample_at(mh_scene *s, uint32_t medium, uint64_t n, const float *u, const float *pos, float *wo, float *pdf,
                        uint32_t flags) {
@@ -1629,11 +1658,11 @@ static int prb_weights_impl(mh_scene *s, uint32_t seed, uint32_t spp, uint32_t s
 // radiance is a small slot too (emitter_slot)
 // ---------------------------------------------------------------------------
 struct Slots {
-    std::vector<int32_t> slot_of_tex, sigma_slot, albedo_slot, emitter_slot;
+    std::vector<int32_t> slot_of_tex, sigma_slot, albedo_slot, emitter_slot, phase_slot;
     std::vector<uint32_t> is_rgb;
     std::vector<size_t> counts;
     std::vector<uint32_t> slot_of_param;
-    uint32_t n_rgb = 0, n_bmp = 0, n_medium_params = 0, n_emitter_params = 0, bmp_tex = 0;
+    uint32_t n_rgb = 0, n_bmp = 0, n_medium_params = 0, n_emitter_params = 0, n_phase_params = 0, bmp_tex = 0;
     uint32_t grid_res[kMaxParams][3] = {};  // large sigma_t slots: the grid's resolution (x, y, z)
     std::vector<float *> corner;            // their corner blocks (upload_slots, corners = true)
     bool fx = false;                        // the blocks hold int64 fixed point (deterministic)
@@ -1646,6 +1675,7 @@ static int build_slots(const mh_scene *s, uint32_t n_params, const uint32_t *par
     P.slot_of_tex.assign(std::max<uint32_t>(s->n_textures, 1), -1);
     P.sigma_slot.assign(std::max<uint32_t>(s->n_media, 1), -1);
     P.albedo_slot = P.sigma_slot;
+    P.phase_slot = P.sigma_slot;
     P.emitter_slot.assign(std::max<size_t>(s->h_emitters.size(), 1), -1);
     P.is_rgb.assign(kMaxParams, 0);
     P.counts.assign(kMaxParams, 0);
@@ -1674,6 +1704,17 @@ static int build_slots(const mh_scene *s, uint32_t n_params, const uint32_t *par
                 small = md.type == MH_MEDIUM_HOMOGENEOUS;
                 cnt = small ? 1 : (size_t)md.grid_res[0] * md.grid_res[1] * md.grid_res[2];
             }
+        } else if (kind == MH_PARAM_MEDIUM_PHASE_G) {
+            if (!vol)
+                return set_error(MH_ERR_UNSUPPORTED, m + "(): medium parameters require the 'prbvolpath' integrator");
+            if (idx >= s->n_media) return set_error(MH_ERR_INVALID_ARGUMENT, a + ": medium index out of bounds");
+            if (s->h_dmedia[idx].phase != MH_PHASE_HG)
+                return set_error(MH_ERR_UNSUPPORTED, m + "(): MH_PARAM_MEDIUM_PHASE_G needs a medium whose phase function "
+                                                         "is MH_PHASE_HG (other phase functions' parameters are not "
+                                                         "differentiable)");
+            ++P.n_medium_params;
+            ++P.n_phase_params;
+            owner = &P.phase_slot[idx]; small = true; cnt = 1;
         } else if (kind == MH_PARAM_EMITTER_RADIANCE) {
             if (idx >= s->h_emitters.size()) return set_error(MH_ERR_INVALID_ARGUMENT, a + ": emitter index out of bounds");
             ++P.n_emitter_params;
@@ -1702,7 +1743,7 @@ static int build_slots(const mh_scene *s, uint32_t n_params, const uint32_t *par
 }
 
 // per-slot device buffers (s->tmp_c, zeroed) and the meta block
-// slot_of_tex | is_rgb | bufs | sigma_slot | albedo_slot | corner | emitter_slot (s->grad_meta)
+// slot_of_tex | is_rgb | bufs | sigma_slot | albedo_slot phase_slot | corner | emitter_slot (s->grad_meta)
 // corners: the grid sigma_t slots scatter into per-cell corner blocks
 // (s->grid_corner, zeroed; launch_corner_gather after the backward) unless
 // MH_GRID_CORNER=0, the block would exceed 16 GiB or cannot be allocated
@@ -1746,7 +1787,8 @@ static hipError_t upload_slots(mh_scene *s, Slots &P, hipStream_t st, std::vecto
     auto al16 = [](size_t x) { return (x + 15) / 16 * 16; };
     const size_t o_slot = 0, o_isrgb = al16(P.slot_of_tex.size() * 4), o_bufs = al16(o_isrgb + kMaxParams * 4),
                  o_sig = al16(o_bufs + kMaxParams * 8), o_alb = al16(o_sig + P.sigma_slot.size() * 4),
-                 o_cor = al16(o_alb + P.albedo_slot.size() * 4), o_em = al16(o_cor + kMaxParams * 8),
+                 o_ph = o_alb + P.albedo_slot.size() * 4,  // phase_slot: straight after albedo_slot (phase_g_backward)
+                 o_cor = al16(o_ph + P.phase_slot.size() * 4), o_em = al16(o_cor + kMaxParams * 8),
                  meta_bytes = al16(o_em + P.emitter_slot.size() * 4);
     std::vector<uint8_t> &meta = P.meta;
     meta.assign(meta_bytes, 0);
@@ -1757,6 +1799,7 @@ static hipError_t upload_slots(mh_scene *s, Slots &P, hipStream_t st, std::vecto
     memcpy(meta.data() + o_alb, P.albedo_slot.data(), P.albedo_slot.size() * 4);
     memcpy(meta.data() + o_cor, P.corner.data(), kMaxParams * 8);
     memcpy(meta.data() + o_em, P.emitter_slot.data(), P.emitter_slot.size() * 4);
+    memcpy(meta.data() + o_ph, P.phase_slot.data(), P.phase_slot.size() * 4);
     // uploaded only when it changes (a new parameter set or reallocated slot
     // buffers), then with a stream sync; repeated calls with the same
     // parameters stay asynchronous
@@ -1777,6 +1820,7 @@ static hipError_t upload_slots(mh_scene *s, Slots &P, hipStream_t st, std::vecto
     ga.sigma_slot = P.n_medium_params ? reinterpret_cast<const int32_t *>(mb + o_sig) : nullptr;
     ga.albedo_slot = P.n_medium_params ? reinterpret_cast<const int32_t *>(mb + o_alb) : nullptr;
     ga.emitter_off = P.n_emitter_params ? (uint32_t)(o_em - o_slot) : 0u;
+    ga.n_phase_g = P.n_phase_params;
     bool any_corner = false;
     for (float *c : P.corner) any_corner = any_corner || c;
     ga.corner = any_corner ? reinterpret_cast<float *const *>(mb + o_cor) : nullptr;
@@ -1837,6 +1881,7 @@ static int render_backward_impl(mh_scene *s, const mh_integrator *in, uint32_t s
     facts.n_rgb = n_rgb;
     facts.n_bmp = n_bmp;
     facts.bmp_slot_bytes = (uint64_t)counts[kMaxRgbParams] * 4;
+    facts.n_phase_params = P.n_phase_params;
     // (several bitmaps: all with the same channel count, as the scatter's
     // transposed issue assumes)
     {

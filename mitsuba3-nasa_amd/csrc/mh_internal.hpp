@@ -29,7 +29,7 @@ struct GradArgs {
     float *const *bufs;          // device: slot -> gradient buffer
     const uint32_t *is_rgb;      // device: slot -> 1 if rgb
     uint32_t n_rgb;              // small (register-accumulated) slots are 0 .. n_rgb-1:
-                                 // rgb textures, medium albedo, homogeneous sigma_t, emitter radiance
+                                 // rgb textures, medium albedo, homogeneous sigma_t, emitter radiance, HG asymmetry
     // the emitter -> radiance slot (or -1) table, as its byte offset from
     // slot_of_tex (both lie in one meta block); 0 when no emitter parameter is
     // listed, which selects the kernel instances without the emitter terms.
@@ -37,10 +37,14 @@ struct GradArgs {
     // arguments of those instances keep their layout.)
     uint32_t emitter_off = 0;
     const int32_t *sigma_slot;   // device: medium -> sigma_t slot or -1 (prbvolpath)
-    const int32_t *albedo_slot;  // device: medium -> albedo slot or -1 (prbvolpath)
+    const int32_t *albedo_slot;  // device: medium -> albedo slot or -1 (prbvolpath); then medium -> g slot or -1
     int32_t lds_slot = -1;       // bitmap slot accumulated per workgroup in LDS (k_prb_backward replay)
     uint32_t lds_floats = 0;     // its size (floats)
     uint32_t lds_offset = 0;     // byte offset of the accumulator in dynamic LDS (set by the launcher)
+    // the '<medium>.phase_function.g' (HG asymmetry) parameters listed; 0 selects the kernel
+    // instances without their terms (PhG = false).  Host only, in the struct's padding like
+    // emitter_off.  Their medium -> slot (or -1) table follows albedo_slot's n_media entries.
+    uint32_t n_phase_g = 0;
     float *const *corner = nullptr;  // device: slot -> per-cell corner block of a grid sigma_t slot or nullptr
                                      // (prbvolpath; gathered into bufs[slot] by launch_corner_gather)
     // MH_FLAG_DETERMINISTIC on the corner blocks: 1 = pre-pass (the largest |item| into fx_max, no
@@ -62,6 +66,7 @@ struct GradArgs {
     float *hot_buf = nullptr;    // bufs[hot_sigma]
     float *hot_corner = nullptr; // corner[hot_sigma] (nullptr: atomics into hot_buf)
 };
+static_assert(sizeof(GradArgs) == 144, "n_phase_g lies in padding: the kernel arguments keep their layout");
 __host__ __device__ inline const int32_t *emitter_slot_table(const int32_t *slot_of_tex, uint32_t emitter_off) {
     return emitter_off ? reinterpret_cast<const int32_t *>(reinterpret_cast<const uint8_t *>(slot_of_tex) + emitter_off)
                        : nullptr;
@@ -99,6 +104,9 @@ hipError_t launch_trace(const DScene &S, bool shadow, uint64_t n, const float *r
 // in is u1[n] u2x[n] u2y[n]
 hipError_t launch_phase_query(const DScene &S, bool sample, uint32_t medium, uint64_t n, const float *in,
                               const float *pos, float *wo_or_value, float *pdf, uint32_t grid, hipStream_t st);
+// mh_phase_eval_grad: wo x[n] y[n] z[n] -> d value / d g [n] of an MH_PHASE_HG medium
+hipError_t launch_phase_eval_grad(const DScene &S, uint32_t medium, uint64_t n, const float *wo, float *dvalue,
+                                  uint32_t grid, hipStream_t st);
 hipError_t launch_render(const DScene &S, const IntegratorParams &in, const LaneMap &lm,
                          uint32_t seed_value, uint32_t n_passes, uint64_t n, uint64_t plane,
                          float *out, unsigned long long *counters, hipStream_t st, int alpha = 0);

@@ -719,7 +719,8 @@ __global__ void k_develop(uint64_t n_px, const float *__restrict__ film, float *
 // <adj, tangent> sum is then dL_c (the medium's sigma_t adjoint mixes the
 // channels, so one replay cannot give all three)
 // ---------------------------------------------------------------------------
-template <bool Vol, bool InLds, int Ph = kPhExt>
+// PhG: the call lists an `hg` medium's asymmetry g (GradArgs::n_phase_g; Vol only)
+template <bool Vol, bool InLds, int Ph = kPhExt, bool PhG = false>
 __global__ void __launch_bounds__(256, Vol ? MH_VOL_WAVES : 1)
 k_render_forward(DScene S, IntegratorParams in, LaneMap lm, uint32_t seed_value, uint64_t n, uint64_t plane,
                  float *__restrict__ out, GradArgs ga, unsigned long long *__restrict__ counters, int alpha) {
@@ -748,8 +749,8 @@ k_render_forward(DScene S, IntegratorParams in, LaneMap lm, uint32_t seed_value,
             for (int c = 0; c < 3; ++c) {
                 Pcg rc = rng;
                 g.fsum = 0.f;
-                prbvol_sample<1, Ph>(S, B, in, rc, r, v3(c == 0 ? 1.f : 0.f, c == 1 ? 1.f : 0.f, c == 2 ? 1.f : 0.f), Lp,
-                                 &g, n_closest, n_shadow);
+                prbvol_sample<1, Ph, PhG>(S, B, in, rc, r, v3(c == 0 ? 1.f : 0.f, c == 1 ? 1.f : 0.f, c == 2 ? 1.f : 0.f),
+                                          Lp, &g, n_closest, n_shadow);
                 d[c] = g.fsum;
             }
             dL = v3(d[0], d[1], d[2]);
@@ -843,7 +844,9 @@ struct PvpWork {
     uint32_t main_cap;
 };
 
-template <bool InLds, int Ph = kPhExt>
+// PhG: the call lists an `hg` medium's asymmetry g (GradArgs::n_phase_g); the
+// instances without it are the kernels of a call that lists none
+template <bool InLds, int Ph = kPhExt, bool PhG = false>
 __global__ void __launch_bounds__(256, MH_VOL_WAVES)
 k_prbvol_backward(DScene S, IntegratorParams in, LaneMap lm, uint32_t seed_value, uint64_t n, int coalesce,
                   const float *__restrict__ grad_in, GradArgs ga, unsigned long long *__restrict__ counters,
@@ -881,14 +884,15 @@ k_prbvol_backward(DScene S, IntegratorParams in, LaneMap lm, uint32_t seed_value
             Pcg rng_primal = rng;  // sampler.clone()
             if (wk.main) {  // single pass: primal + logged adjoint terms, replay only on overflow
                 MainLog ml{wk.main, nl.stride, wk.main_cap, nl.t, 0u, false};
-                const V3 Lp = prbvol_sample<2, Ph>(S, B, in, rng_primal, r, dL, v3(0, 0, 0), &g, n_closest, n_shadow,
-                                                   nullptr, &nl, &ml);
-                if (!ml.overflow) pvp_log_apply(S, ml, Lp, g);
-                else prbvol_sample<3, Ph>(S, B, in, rng, r, dL, Lp, &g, n_closest, n_shadow);
+                const V3 Lp = prbvol_sample<2, Ph, PhG>(S, B, in, rng_primal, r, dL, v3(0, 0, 0), &g, n_closest, n_shadow,
+                                                        nullptr, &nl, &ml);
+                if (!ml.overflow) pvp_log_apply<PhG>(S, ml, Lp, g);
+                else prbvol_sample<3, Ph, PhG>(S, B, in, rng, r, dL, Lp, &g, n_closest, n_shadow);
             } else {
                 V3 Lp = prbvol_sample<0, Ph>(S, B, in, rng_primal, r, v3(0, 0, 0), v3(0, 0, 0), nullptr, n_closest,
                                              n_shadow);
-                prbvol_sample<1, Ph>(S, B, in, rng, r, dL, Lp, &g, n_closest, n_shadow, nullptr, wk.log ? &nl : nullptr);
+                prbvol_sample<1, Ph, PhG>(S, B, in, rng, r, dL, Lp, &g, n_closest, n_shadow, nullptr,
+                                          wk.log ? &nl : nullptr);
             }
         }
         if (!wk.log) break;
@@ -976,6 +980,23 @@ k_phase_eval(DScene S, uint32_t medium, uint64_t n, const float *__restrict__ wo
         }
     }
 }
+// mh_phase_eval_grad: d phase_eval / d g of an `hg` medium, as the PhG instances
+// of prbvol_sample form it (value * d ln p / d g); i < n bounds every access
+__global__ void __launch_bounds__(256)
+k_phase_eval_grad(DScene S, uint32_t medium, uint64_t n, const float *__restrict__ wo, float *__restrict__ dvalue) {
+    const DMedium &m = S.media[medium];
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const V3 w = v3(wo[i], wo[n + i], wo[2 * n + i]);
+        dvalue[i] = phase_eval(S, m, w) * hg_dlog_dg(m.g, -w.z);
+    }
+}
+hipError_t launch_phase_eval_grad(const DScene &S, uint32_t medium, uint64_t n, const float *wo, float *dvalue,
+                                  uint32_t grid, hipStream_t st) {
+    if (n == 0 || grid == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_phase_eval_grad, dim3(grid), dim3(256), 0, st, S, medium, n, wo, dvalue);
+    return hipGetLastError();
+}
 hipError_t launch_phase_query(const DScene &S, bool sample, uint32_t medium, uint64_t n, const float *in,
                               const float *pos, float *wo_or_value, float *pdf, uint32_t grid, hipStream_t st) {
     if (n == 0 || grid == 0) return hipSuccess;
@@ -1005,7 +1026,13 @@ hipError_t launch_render_forward(const DScene &S, const IntegratorParams &in, co
     const size_t sh = lds_bytes(S, bs);
     const dim3 g(blocks_for(n, bs)), b(bs);
     variant::render_forward(variant_facts(S), in.type, [&](auto Vol, auto L, auto Ph) {
-        hipLaunchKernelGGL((k_render_forward<Vol, L, Ph>), g, b, sh, st, S, in, lm, seed_value, n, plane, out, ga, counters, alpha);
+        if constexpr (Vol) {
+            variant::phase_g(ga.n_phase_g != 0, [&](auto G) {
+                hipLaunchKernelGGL((k_render_forward<Vol, L, Ph, G>), g, b, sh, st, S, in, lm, seed_value, n, plane, out, ga, counters, alpha);
+            });
+        } else {
+            hipLaunchKernelGGL((k_render_forward<Vol, L, Ph>), g, b, sh, st, S, in, lm, seed_value, n, plane, out, ga, counters, alpha);
+        }
     });
     return hipGetLastError();
 }
@@ -1278,7 +1305,9 @@ hipError_t launch_prb_backward(const DScene &S, const IntegratorParams &in, cons
             if (e != hipSuccess) return e;
         }
         variant::dispatch(variant::vol_lane(F), [&](auto, auto Ph, auto L, auto, auto) {
-            hipLaunchKernelGGL((k_prbvol_backward<L, Ph>), g, b, sh, st, S, in, lm, seed_value, n, coalesce, grad_in, ga, counters, wk);
+            variant::phase_g(ga.n_phase_g != 0, [&](auto G) {
+                hipLaunchKernelGGL((k_prbvol_backward<L, Ph, G>), g, b, sh, st, S, in, lm, seed_value, n, coalesce, grad_in, ga, counters, wk);
+            });
         });
         return hipGetLastError();
     }

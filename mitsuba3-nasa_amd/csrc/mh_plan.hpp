@@ -88,6 +88,7 @@ struct Facts {
     uint32_t n_rgb = 0, n_bmp = 0;
     bool bmp_same_ch = true;      // every bitmap parameter has the same channel count
     uint64_t bmp_slot_bytes = 0;  // bytes of the first bitmap slot
+    uint32_t n_phase_params = 0;  // '<medium>.phase_function.g' keys (prbvolpath)
 };
 
 // ---- mh_render --------------------------------------------------------------
@@ -175,7 +176,9 @@ inline BackwardPlan plan_backward(const Facts &f, const PlanEnv &e) {
         p.pvp_log = true;
         p.main_cap = e.pvp_single_off ? 0u : e.pvp_main_cap ? e.pvp_main_cap : kPvpMainCap;
         p.nee_cap = e.pvp_nee_cap ? e.pvp_nee_cap : kPvpNeeCap;
-        p.sched = p.main_cap && f.vs_ok && !e.pvp_sched_off;
+        // a phase-function parameter: the per-lane kernel with its logs (k_prbvol_backward's PhG
+        // instances); the scheduler machines, at 248-256 VGPRs, have no instance with its terms
+        p.sched = p.main_cap && f.vs_ok && !e.pvp_sched_off && f.n_phase_params == 0;
     }
     return p;
 }

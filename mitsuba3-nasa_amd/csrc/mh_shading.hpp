@@ -6,6 +6,7 @@
 
 #include "mh_device.hpp"
 #include "mh_internal.hpp"
+#include "mh_phase_grad.hpp"
 
 namespace mh {
 
@@ -3410,6 +3411,21 @@ MH_DEV void albedo_backward(uint32_t med, V3 adj, GradCtx &g) {
     else acc_add(g, k, adj);
 }
 
+// adjoint of an `hg` medium's asymmetry g (a small slot of one float); forward
+// mode: adj * tangent.  The two terms of a real scatter event (prbvolpath.py:
+// 257-270 and :283-289) end here; the media without the key have slot -1.
+// The medium -> slot table follows albedo_slot's n_media entries in the meta
+// block (GradArgs::albedo_slot), so that GradCtx keeps its members and the
+// kernels without these terms their register allocation; called by the PhG
+// instances only, whose calls list such a key, so the table is there.
+MH_DEV void phase_g_backward(const DScene &S, uint32_t med, float adj, GradCtx &g) {
+    if (!g.albedo_slot) return;
+    const int32_t k = g.albedo_slot[S.n_media + med];
+    if (k < 0) return;
+    if (g.fwd) g.fsum += adj * g.bufs[k][0];
+    else acc_add(g, k, v3(adj, 0.f, 0.f));
+}
+
 // Per-thread log of the gradient steps of one NEE walk (the adjoint pass of
 // k_prbvol_backward).  The reference replays the walk with the cloned sampler
 // to back-propagate dL * adj_emitted through every tr_multiplier
@@ -3544,6 +3560,7 @@ MH_DEV V3 pvp_sample_emitter(const DScene &S, const LdsBvh &B, const MEI &mei_re
 // Entry: 4 float4 at ((4 j + q) * stride + t):
 //   q0 (p, bits: 1 surface | 2 scatter | index << 2)   q1 (P, uv.x)
 //   q2 (dL / max(1e-8, w), uv.y)                       q3 (dws, dwa) or (cos, 0, 0, 0)
+// bits 3 (PhG instances): an `hg` scatter's phase sample, q2 (dL, 0), q3 ((d p / d g) / max(1e-8, p), 0, 0, 0)
 struct MainLog {
     float4 *buf;
     uint32_t stride, cap, t, n;
@@ -3621,7 +3638,11 @@ MH_DEV void charge_walk_log(const DScene &S, const float4 *e, uint32_t stride, u
 // Mode 0: primal; 1: adjoint replay (L = primal radiance); 2: primal + MainLog
 // + NEE gradients (single pass); 3: adjoint replay without the NEE gradients
 // (the fallback of a Mode-2 path whose log overflowed)
-template <int Mode, int Ph = kPhExt>
+// PhG: the call lists an `hg` medium's asymmetry g (GradArgs::n_phase_g): the
+// two terms of a real scatter event, the NEE term charged on the spot and the
+// sample term charged with L (Adj) or logged (Log, a MainLog entry of bits 3).
+// The instances without it are the kernels of a call that lists none.
+template <int Mode, int Ph = kPhExt, bool PhG = false>
 MH_DEV V3 prbvol_sample(const DScene &S, const LdsBvh &B, const IntegratorParams &in, Pcg &rng, RayT ray,
                         V3 dL, V3 L, GradCtx *g, uint32_t &n_closest, uint32_t &n_shadow,
                         bool *valid_out = nullptr, NeeLog *nl = nullptr, MainLog *ml = nullptr) {
@@ -3778,6 +3799,15 @@ MH_DEV V3 prbvol_sample(const DScene &S, const LdsBvh &B, const IntegratorParams
             const float mis = mis_weight(ds.pdf, nee_pdf);
             const V3 contrib = ((throughput * nee_w) * mis) * emitted;
             L = Adj ? L + (-contrib) : L + contrib;
+            if constexpr (PhG && NeeGrad) {
+                // backward(dL * contrib) through nee_weight = phase_val (prbvolpath.py:257-270; mis_weight is
+                // detached): contrib is linear in p, so its derivative is contrib * d ln p / d g
+                if (active_e_medium && S.media[med].phase == MH_PHASE_HG) {
+                    const float K = (dL.x * contrib.x + dL.y * contrib.y) + dL.z * contrib.z;
+                    if (K != 0.f)  // (no emitter sample: ds.d is not a direction)
+                        phase_g_backward(S, med, K * hg_dlog_dg(S.media[med].g, -mei_to_local(mei, ds.d).z), *g);
+                }
+            }
             if (NeeGrad) {
                 if (g->emitter_slot && S.n_emitters) {
                     // backward(dL * contrib) through the sampled emitter's radiance (prbvolpath.py:346-351:
@@ -3811,6 +3841,19 @@ MH_DEV V3 prbvol_sample(const DScene &S, const LdsBvh &B, const IntegratorParams
             float ph_pdf;
             const V3 wo = phase_sample<Ph>(S, S.media[med], s2x, s2y, ph_pdf, s1, blend_w);
             act_scatter = act_scatter && ph_pdf > 0.f;
+            if constexpr (PhG && (Adj || Log)) {
+                // Lo = phase_eval * detach(L / max(1e-8, phase_eval)) (prbvolpath.py:283-289), the medium twin of
+                // the surface term below: (dL . L) * (d p / d g)(wo) / max(1e-8, p(wo)), L the radiance beyond
+                // this vertex (its NEE already taken off); value == pdf for `hg`
+                if (act_scatter && S.media[med].phase == MH_PHASE_HG) {
+                    const float c = (ph_pdf * hg_dlog_dg(S.media[med].g, -wo.z)) / fmaxf(1e-8f, ph_pdf);
+                    if (Adj) phase_g_backward(S, med,((dL.x * L.x + dL.y * L.y) + dL.z * L.z) * c, *g);
+                    if (Log)
+                        ml->add(make_float4(0.f, 0.f, 0.f, __uint_as_float(3u | (med << 2))),
+                                make_float4(L.x, L.y, L.z, 0.f), make_float4(dL.x, dL.y, dL.z, 0.f),
+                                make_float4(c, 0.f, 0.f, 0.f));
+                }
+            }
             if (act_scatter) {
                 ray = spawn_ray(mei.p, v3(0.f, 0.f, 0.f), mei_to_world(mei, wo));
                 needs_intersection = true;
@@ -3863,9 +3906,17 @@ MH_DEV V3 prbvol_sample(const DScene &S, const LdsBvh &B, const IntegratorParams
 
 // one logged L-dependent term (q0..q3: a MainLog entry) of a path whose
 // radiance is now L_total
+// PhG: bits 3 is an `hg` scatter's sample term: q2 = dL, q3.x = (d p / d g) / max(1e-8, p)
+template <bool PhG = false>
 MH_DEV void pvp_log_entry(const DScene &S, float4 q0, float4 q1, float4 q2, float4 q3, V3 Ltot, GradCtx &g) {
     const uint32_t bits = __float_as_uint(q0.w), idx = bits >> 2;
     const V3 Lsuf = Ltot - v3(q1.x, q1.y, q1.z);  // prbvolpath.py: L - (contributions so far)
+    if constexpr (PhG) {
+        if ((bits & 3u) == 3u) {
+            phase_g_backward(S, idx, ((q2.x * Lsuf.x + q2.y * Lsuf.y) + q2.z * Lsuf.z) * q3.x, g);
+            return;
+        }
+    }
     const V3 up = v3(q2.x * Lsuf.x, q2.y * Lsuf.y, q2.z * Lsuf.z);
     if (bits & 1u) {
         const V3 adj = (up * kInvPi) * q3.x;
@@ -3878,6 +3929,7 @@ MH_DEV void pvp_log_entry(const DScene &S, float4 q0, float4 q1, float4 q2, floa
 }
 
 // the logged L-dependent terms of a path whose radiance is now L_total
+template <bool PhG = false>
 MH_DEV void pvp_log_apply(const DScene &S, const MainLog &ml, V3 Ltot, GradCtx &g) {
     for (uint32_t j0 = 0; j0 < ml.n; j0 += kLogBatchMain) {
         float4 q[kLogBatchMain][4];
@@ -3891,7 +3943,7 @@ MH_DEV void pvp_log_apply(const DScene &S, const MainLog &ml, V3 Ltot, GradCtx &
 #pragma unroll
         for (uint32_t b = 0; b < kLogBatchMain; ++b) {
             if (j0 + b >= ml.n) break;
-            pvp_log_entry(S, q[b][0], q[b][1], q[b][2], q[b][3], Ltot, g);
+            pvp_log_entry<PhG>(S, q[b][0], q[b][1], q[b][2], q[b][3], Ltot, g);
         }
     }
 }

@@ -122,6 +122,14 @@ bool dispatch(const VolKernel &k, F &&f) {
     return select_home(k.home, f, flag(k.fresh), among<kPhExt, kPhBlend>(k.ph));
 }
 
+// ---- the last argument of k_prbvol_backward<InLds, Ph, PhG> and k_render_forward<true, InLds, Ph, PhG>:
+// ---- f(PhG), nested in the selections above and below.  PhG: the call lists an `hg` medium's asymmetry g
+// (GradArgs::n_phase_g != 0) and gets the instances with its two adjoint terms; a call without one launches
+// the kernels it launched before.  (The scheduler machines have no such instance: plan_backward turns `sched`
+// off for such a call, mh_plan.hpp.)
+template <class F>
+bool phase_g(bool key_listed, F &&f) { return select(f, flag(key_listed)); }
+
 // ---- k_render<Kind, InLds, Ph>: f(Kind, InLds, Ph).  Kind: mh_integrator::type (what is none of
 // the others renders as `path`); kPhBlend: a volumetric integrator on a scene with a blend medium
 template <class F>

@@ -52,6 +52,7 @@ PARAM_KIND_MASK = 0xF0000000
 PARAM_MEDIUM_SIGMA_T = 0x10000000
 PARAM_MEDIUM_ALBEDO = 0x20000000
 PARAM_EMITTER_RADIANCE = 0x30000000
+PARAM_MEDIUM_PHASE_G = 0x40000000
 
 FLAG_DEVICE_POINTERS = 1 << 0
 FLAG_ACCUMULATE = 1 << 1
@@ -152,6 +153,7 @@ EXPORTS = [
     "mh_render_backward_sharded", "mh_scene_update_emitter", "mh_scene_set_phase_table", "mh_phase_sample",
     "mh_phase_eval", "mh_scene_set_phase_blend", "mh_scene_set_phase_blend_table",
     "mh_scene_update_phase_blend_weight", "mh_phase_sample_at", "mh_phase_eval_at",
+    "mh_scene_update_medium_phase", "mh_phase_eval_grad",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -200,6 +202,8 @@ def lib():
     L.mh_scene_update_phase_blend_weight.argtypes = [vp, u32, PF, u64]
     L.mh_phase_sample_at.argtypes = [vp, u32, u64, vp, vp, vp, vp, u32]
     L.mh_phase_eval_at.argtypes = [vp, u32, u64, vp, vp, vp, u32]
+    L.mh_scene_update_medium_phase.argtypes = [vp, u32, f32]
+    L.mh_phase_eval_grad.argtypes = [vp, u32, u64, vp, vp, u32]
     L.mh_render.argtypes = [vp, C.POINTER(Integrator), u32, u32, u32, u32, vp, u32, C.POINTER(Stats)]
     L.mh_develop.argtypes = [vp, vp, vp, u32]
     L.mh_render_samples.argtypes = [vp, C.POINTER(Integrator), u32, u32, u32, u32, vp, u32]

@@ -63,7 +63,10 @@ class SceneParameters:
     parameters on the hot path: '<bsdf>.reflectance.value' / '.data' and the
     medium parameters '<medium>.sigma_t.data' (grid, shape (z, y, x, 1) as the
     reference's TensorXf), '<medium>.sigma_t.value' (homogeneous) and
-    '<medium>.albedo.value', and the emitters' radiance:
+    '<medium>.albedo.value', an `hg` medium's asymmetry
+    '<medium>.phase_function.g' (shape (1,); update() refuses a value outside
+    (-1, 1), clamping an optimizer's step is the caller's job as in the
+    reference), and the emitters' radiance:
     '<shape>.emitter.radiance.value' (area), '<name>.radiance.value'
     (constant) and '<name>.irradiance.value' (directional)."""
 
@@ -86,6 +89,8 @@ class SceneParameters:
                 v = torch.tensor([scene.medium(idx).sigma_t_const], dtype=torch.float32)
             elif kind == "medium_albedo":
                 v = torch.tensor(list(scene.medium(idx).albedo), dtype=torch.float32)
+            elif kind == "medium_phase_g":
+                v = torch.tensor([scene.medium(idx).g], dtype=torch.float32)
             elif kind == "emitter_radiance":
                 v = torch.tensor(list(scene.emitter(idx).radiance), dtype=torch.float32)
             elif kind == "phase_table":
@@ -145,6 +150,8 @@ class SceneParameters:
             return A.PARAM_MEDIUM_SIGMA_T | idx
         if kind == "medium_albedo":
             return A.PARAM_MEDIUM_ALBEDO | idx
+        if kind == "medium_phase_g":
+            return A.PARAM_MEDIUM_PHASE_G | idx
         if kind == "emitter_radiance":
             return A.PARAM_EMITTER_RADIANCE | idx
         return idx
@@ -199,6 +206,14 @@ class SceneParameters:
                 for h in self.scene._handles.values():   # the blend again: tabulated children keep their tables
                     rec = self.scene.phase_blends[idx[0]].record()
                     A.check(L.mh_scene_set_phase_blend(h, idx[0], C.byref(rec)))
+            elif kind == "medium_phase_g":
+                # the loader's check (hg.cpp's constructor), before anything is stored
+                g = float(arr[0])
+                if not (-1.0 < g < 1.0):
+                    raise RuntimeError("The asymmetry parameter must lie in the interval (-1, 1)!")
+                self.scene.medium(idx).g = float(np.float32(g))
+                for h in self.scene._handles.values():
+                    A.check(L.mh_scene_update_medium_phase(h, idx, g))
             elif kind in ("grid", "medium_sigma_t", "medium_albedo"):
                 m = self.scene.medium(idx)
                 if kind == "grid":

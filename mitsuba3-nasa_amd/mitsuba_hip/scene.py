@@ -401,6 +401,7 @@ class _Builder:
             if g >= 1.0 or g <= -1.0:
                 raise RuntimeError("The asymmetry parameter must lie in the interval (-1, 1)!")
             m.phase, m.g = A.PHASE_HG, float(np.float32(g))
+            self.params[name + ".phase_function.g"] = ("medium_phase_g", len(self.media))   # hg.cpp:61-63
         elif ph.get("type") == "isotropic":
             m.phase, m.g = A.PHASE_ISOTROPIC, 0.0
         elif ph.get("type") == "rayleigh":

@@ -58,8 +58,11 @@ def main():
     ap.add_argument("--phase", default="hg", choices=["hg", "rayleigh", "tab", "blend"],
                     help="the medium's phase function: hg (g = 0.85), rayleigh, that hg as an 1,801-node tabphase, "
                          "or a blendphase of rayleigh and that table with a 64^3 weight grid")
+    ap.add_argument("--phase-g", action="store_true",
+                    help="prbvolpath: also differentiate the HG asymmetry (medium1.phase_function.g); the backward "
+                         "then runs the per-sample kernel with its logs instead of the scheduler")
     a = ap.parse_args()
-    a.no_cpu = a.no_cpu or a.phase != "hg"   # the oracle has only isotropic and hg
+    a.no_cpu = a.no_cpu or a.phase != "hg" or a.phase_g   # the oracle has only isotropic and hg, and no g gradient
     import torch
     import mitsuba_hip as mi
     from mitsuba_hip import _abi as A
@@ -125,7 +128,7 @@ def vs_sub(A):
 def bench_prbvolpath(a, mi, A, scene, t_load):
     import torch
     params = mi.traverse(scene)
-    keys = ["medium1.sigma_t.data", "medium1.albedo.value"]
+    keys = ["medium1.sigma_t.data", "medium1.albedo.value"] + (["medium1.phase_function.g"] if a.phase_g else [])
     gi = torch.full((a.res, a.res, 3), 1.0 / (a.res * a.res * 3), device="cuda")
     sf, sb = A.Stats(), A.Stats()
     scene_f, run = scene, None
@@ -160,6 +163,7 @@ def bench_prbvolpath(a, mi, A, scene, t_load):
            "unit": "Msamples/s", "ms_per_step": round(dt * 1e3, 3),
            "fwd_kernel_ms": round(sum(kf) / len(kf), 3), "bwd_kernel_ms": round(sum(kb) / len(kb), 3),
            "grad_sigma_t_abs_sum": float(g[0].abs().sum()), "grad_albedo": [float(x) for x in g[1]],
+           "keys": keys, "grad_g": float(g[2][0]) if a.phase_g else None,
            "deterministic": a.deterministic, "overlap": a.overlap, "bwd_subphases": sub,
            "fwd_rays_closest_per_sample": round(sf.rays_closest / n, 3),
            "fwd_rays_shadow_per_sample": round(sf.rays_shadow / n, 3),
