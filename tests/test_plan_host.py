@@ -69,6 +69,19 @@ def test_chunk_limit(cases):
     assert cases["split_512x512_256_two_off"] == dict(chunk_px=131072, n_chunks=2, two=0)
 
 
+def test_split_ragged_shapes(cases):
+    # tests/ragged_cases.py at 1024 samples per chunk: chunk_px = 1024 // S, no whole number of waves
+    assert cases["split_ragged_tiny"] == dict(chunk_px=7, n_chunks=1, two=0)        # 341 > 7 pixels
+    assert cases["split_ragged_odd"] == dict(chunk_px=91, n_chunks=1, two=0)        # 204 > 91
+    assert cases["split_ragged_over16"] == dict(chunk_px=60, n_chunks=3, two=1)     # 1024 // 17, 180 pixels
+    assert cases["split_ragged_over32"] == dict(chunk_px=31, n_chunks=3, two=1)     # 1024 // 33, 66 pixels
+    assert cases["split_ragged_chunks"] == dict(chunk_px=85, n_chunks=7, two=1)     # 1024 // 12, 540 pixels
+    assert cases["split_ragged_chunks1s"] == dict(chunk_px=85, n_chunks=7, two=0)
+    for name in ("slabs12_0_4", "slabs12_4_7", "slabs12_7_12"):                     # 256, 341, 204 > 135
+        assert cases["split_ragged_" + name] == dict(chunk_px=135, n_chunks=1, two=0)
+    assert cases["split_ragged_slab16_3_10"] == dict(chunk_px=91, n_chunks=1, two=0)  # 146 > 91
+
+
 def test_render_two_streams(cases):
     split = dict(engine="wavefront", mode=2, chunk_px=512, n_chunks=2, two=1, err=0)
     whole = dict(engine="wavefront", mode=2, chunk_px=1024, n_chunks=1, two=0, err=0)

@@ -88,6 +88,17 @@ int main() {
     put("split_odd", plan::split_chunks(1025, 512, kWfMax, true));
     put("split_512x512_256", plan::split_chunks(512 * 512, 256, kWfMax, true));
     put("split_512x512_256_two_off", plan::split_chunks(512 * 512, 256, kWfMax, false));
+    // the launch shapes of tests/ragged_cases.py (W x H pixels, S samples per pixel) at 1024 samples per chunk
+    put("split_ragged_tiny", plan::split_chunks(7 * 1, 3, 1024, true));
+    put("split_ragged_odd", plan::split_chunks(13 * 7, 5, 1024, true));
+    put("split_ragged_over16", plan::split_chunks(20 * 9, 17, 1024, true));
+    put("split_ragged_over32", plan::split_chunks(11 * 6, 33, 1024, true));
+    put("split_ragged_chunks", plan::split_chunks(27 * 20, 12, 1024, true));
+    put("split_ragged_chunks1s", plan::split_chunks(27 * 20, 12, 1024, false));
+    put("split_ragged_slabs12_0_4", plan::split_chunks(27 * 5, 4, 1024, true));
+    put("split_ragged_slabs12_4_7", plan::split_chunks(27 * 5, 3, 1024, true));
+    put("split_ragged_slabs12_7_12", plan::split_chunks(27 * 5, 5, 1024, true));
+    put("split_ragged_slab16_3_10", plan::split_chunks(13 * 7, 7, 1024, true));
 
     // ---- plan_render ----
     const plan::Facts big = facts(PATH, 8, 32, 32, 512), tiny = facts(PATH, 8, 16, 16, 8);
