@@ -118,7 +118,7 @@ struct mh_scene {
     bool own_stream = false;
     DScene S{};
     // device buffers
-    DevBuf nodes, nodes4, primsc, stack_ovf, prims, prim_pairs, key_sp, shapes, bsdf_type, bsdf_tex, textures, emitters, positions, normals,
+    DevBuf nodes, nodes4, primsc, stack_ovf, prims, prim_pairs, key_sp, shade_recs, shapes, bsdf_type, bsdf_tex, textures, emitters, positions, normals,
         texcoords, faces, texels, media, grid;
     DevBuf phase_tab;  // the tabulated phase functions' tables, one after the other (DScene::phase_tab)
     std::vector<std::vector<PhaseRec>> h_phase_tabs;  // per medium (empty: none set)
@@ -574,6 +574,17 @@ int mh_scene_create(const mh_scene_desc *desc, int device, void *stream, mh_scen
     S.rfilter_radius = sn.rfilter_radius;
     memcpy(S.filter_coeff, sn.filter_coeff, sizeof(S.filter_coeff));
     S.sampler_seed = sn.sampler_seed;
+    // shade records of the fused bounce kernels, for the scenes those take (the packet engine's, with
+    // tables that fit LDS): built on the device from the tables uploaded above (same stream), once --
+    // no update call changes geometry, a shape's bsdf or emitter, or a bsdf's type or texture index
+    S.shade_recs = nullptr;
+    if (wf_shade_records() && bvh.n_prims <= wf_packet_max_prims() && S.tab_bytes != 0) {
+        if (upload(s->shade_recs, (const ShadeRec *)nullptr, bvh.n_prims, st) != hipSuccess)
+            return fail(MH_ERR_OUT_OF_MEMORY, "mh_scene_create: shade record allocation failed");
+        S.shade_recs = s->shade_recs.as<ShadeRec>();
+        if (launch_build_shade_recs(S, s->shade_recs.as<ShadeRec>(), st) != hipSuccess)
+            return fail(MH_ERR_HIP, "mh_scene_create: shade record kernel failed");
+    }
     if (hipEventCreate(&s->ev0) != hipSuccess || hipEventCreate(&s->ev1) != hipSuccess)
         return fail(MH_ERR_HIP, "mh_scene_create: hipEventCreate failed");
     if (hipStreamSynchronize(st) != hipSuccess) return fail(MH_ERR_HIP, "mh_scene_create: upload sync failed");
@@ -586,7 +597,7 @@ int mh_scene_destroy(mh_scene *s) {
     if (s->comm) comm_attach(s->comm, -1);
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
-    for (DevBuf *b : {&s->nodes, &s->nodes4, &s->primsc, &s->stack_ovf, &s->prims, &s->prim_pairs, &s->key_sp, &s->shapes, &s->bsdf_type, &s->bsdf_tex, &s->textures,
+    for (DevBuf *b : {&s->nodes, &s->nodes4, &s->primsc, &s->stack_ovf, &s->prims, &s->prim_pairs, &s->key_sp, &s->shade_recs, &s->shapes, &s->bsdf_type, &s->bsdf_tex, &s->textures,
                       &s->emitters, &s->positions, &s->normals, &s->texcoords, &s->faces, &s->texels,
                       &s->media, &s->grid, &s->phase_tab, &s->work, &s->film_tmp, &s->film4, &s->alpha_px, &s->counters, &s->grad_meta, &s->tmp_a, &s->tmp_b,
                       &s->tmp_c, &s->tmp_d, &s->tmp_e, &s->weights_tmp, &s->wf_ws, &s->wf_ctr, &s->wf_ws_prb, &s->wf_partial, &s->gw, &s->wf_carry, &s->wf_ws_bmp, &s->wf_ws_det, &s->pvp_log, &s->pvp_main, &s->pvp_ovf, &s->grid_corner, &s->fx_word, &s->bmp_fx,

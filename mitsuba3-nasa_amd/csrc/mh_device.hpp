@@ -122,6 +122,30 @@ struct DShape {                 // shading-time shape record
     uint32_t interior, exterior, pad3;  // media (MH_INVALID = none)
 };
 
+// 64 B: what shading needs of a primitive and what stays the same from scene
+// creation to destruction, by scene-order key (the index of DScene::key_sp).
+// Built on the device by compute_si itself (k_build_shade_recs), so n, s and
+// t hold the bits the per-hit code produces; the shading normal equals n
+// whenever the frame is constant.  A triangle of a mesh with vertex normals
+// has no constant frame: its record keeps n and, in s, dp_du (both still
+// per-triangle constants), and t is unused.  Indices only, never a parameter
+// value: a parameter update needs no hook.  The fused bounce kernels stage the
+// table into LDS and read one record per closest hit (compute_si_rec).
+struct alignas(16) ShadeRec {
+    float n[3], s[3], t[3];
+    uint32_t shape, prim, bsdf;     // bsdf: MH_INVALID for none
+    uint32_t emitter, tex;          // tex: the reflectance texture of a diffuse bsdf (else 0)
+    uint32_t flags;                 // kSr* in the low byte; a triangle: its mesh's vertex_offset above it
+    uint32_t face;                  // a triangle: face_offset + prim, its row of DScene::faces
+};
+static_assert(sizeof(ShadeRec) == 64, "a shade record is four 16-byte LDS reads");
+constexpr uint32_t kSrRect = 1u;       // the primitive is a rectangle (else a triangle)
+constexpr uint32_t kSrConst = 2u;      // n, s, t hold for every hit (else: s is dp_du, the frame is built per hit)
+constexpr uint32_t kSrDiffuse = 4u;    // its bsdf is diffuse
+constexpr uint32_t kSrTexcoords = 8u;  // its mesh has texture coordinates
+// vertex_offset fits: the fused kernels take scenes whose tables, vertices included, are within 16 KiB
+constexpr uint32_t kSrVertexShift = 8;
+
 struct DTexture {
     uint32_t type, width, height, channels;
     uint64_t data_offset;
@@ -245,6 +269,7 @@ struct DScene {                 // kernel argument (by value)
     const PhaseRec *phase_tab;    // the tabulated phase functions' tables and the blends' records (DMedium::tab_offset; nullptr: none)
     uint32_t phase_tab_bytes;     // their size
     uint32_t phase_lds_bytes;     // per launch: phase_tab_bytes when k_vol_sched stages them into LDS, else 0
+    const ShadeRec *shade_recs;   // per scene-order key (the fused bounce kernels; nullptr: none built)
 };
 
 // lane -> (pixel, sample) map of one render call (sample-slab aware)

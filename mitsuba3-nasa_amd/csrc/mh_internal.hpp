@@ -137,6 +137,11 @@ uint32_t wf_blocks(int cus, bool shared = false);  // wavefront workgroups for a
 uint32_t wf_packet_max_prims();  // largest scene (primitives) the packet engine traces
 bool wf_fused(const DScene &S);  // launch_wavefront runs the fused bounce kernel  // grid rounded to whole queue segments
 variant::Facts variant_facts(const DScene &S);  // what the kernel-variant selectors read of a scene and the environment
+// the fused bounce kernels' per-primitive shade records (ShadeRec): whether this build reads them, and the
+// kernel that fills S.n_prims of them from S's tables (mh_scene_create, once: geometry is never updated)
+struct ShadeRec;
+bool wf_shade_records();
+hipError_t launch_build_shade_recs(const DScene &S, ShadeRec *out, hipStream_t st);
 // One bitmap parameter on the fused PRB wavefront: the bounce kernel logs a
 // record per bitmap vertex, a scatter pass turns the records into texel
 // gradients once the chunk's paths have ended (mh_wavefront.hip).

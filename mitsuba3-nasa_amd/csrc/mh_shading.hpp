@@ -965,12 +965,27 @@ MH_DEV void stage_pair_records(const DScene &S, float *dst) {
     }
 }
 __host__ __device__ inline uint32_t align16(uint32_t x) { return (x + 15u) & ~15u; }
-// dynamic LDS of the fused bounce kernels: tables | stacks | pair records | scratch
+// Shade records (ShadeRec, mh_device.hpp) in the fused bounce kernels: staged
+// into LDS beside the pair records and read once per closest hit in place of
+// key_sp, the shape -> face / bsdf -> texture chain and the frame arithmetic
+// (compute_si_rec).  MH_SHADE_REC=0 builds the kernels without them.
+#ifndef MH_SHADE_REC
+#define MH_SHADE_REC 1
+#endif
+MH_DEV void stage_shade_records(const DScene &S, uint4 *dst) {
+    const uint4 *src = reinterpret_cast<const uint4 *>(S.shade_recs);
+    const uint32_t total = S.n_prims * (uint32_t)(sizeof(ShadeRec) / 16u);
+    for (uint32_t i = threadIdx.x; i < total; i += 256u) dst[i] = src[i];  // the fused kernels' block size
+}
+// dynamic LDS of the fused bounce kernels: tables | stacks | pair records | shade records | scratch
 __host__ __device__ inline uint32_t fused_pairs_offset(const DScene &S) {
     return align16(S.tab_bytes + 16u * S.stack_size);
 }
-__host__ __device__ inline uint32_t fused_scratch_offset(const DScene &S) {
+__host__ __device__ inline uint32_t fused_shade_offset(const DScene &S) {
     return fused_pairs_offset(S) + align16(S.n_prims * kPairRecFloats * 4u);
+}
+__host__ __device__ inline uint32_t fused_scratch_offset(const DScene &S) {
+    return fused_shade_offset(S) + (MH_SHADE_REC ? S.n_prims * (uint32_t)sizeof(ShadeRec) : 0u);
 }
 __host__ __device__ inline uint32_t fused_lds_bytes(const DScene &S) {
     return fused_scratch_offset(S) + 4u * kDeferScratch;
@@ -1104,7 +1119,9 @@ MH_DEV void run_deferred(const Defer &df, const RayT r, bool act, PHit &h) {
 // are deferred and compacted (dfr: LDS pair records + the wave's scratch).
 // Pre: the rectangle tests' division-free early exit (rect_separated; the
 // non-generating PRB bounce leaves it out: 2 more VGPRs spill there)
-template <bool Shadow, bool Def = false, bool Pre = true>
+// KeyOnly: a closest hit returns its key, t, u, v and leaves shape and prim
+// unset (no key_sp load: the caller reads the key's shade record)
+template <bool Shadow, bool Def = false, bool Pre = true, bool KeyOnly = false>
 MH_DEV Hit packet_batch(const Node *gnodes, const Prim *gprims, const Prim *gpairs, const uint2 *key_sp, uint32_t *ws, uint32_t stride,
                         const RayT r, bool act, const float *dfr_recs = nullptr, uint8_t *dfr_scratch = nullptr) {
     const V3 inv = safe_inv_dir(r.d), ood = r.o * inv;
@@ -1178,9 +1195,11 @@ MH_DEV Hit packet_batch(const Node *gnodes, const Prim *gprims, const Prim *gpai
     if (Shadow) {
         hit.shape = ph.occl ? 0u : MH_INVALID;  // occluded / not (the shadow consumers' test)
     } else if (ph.key != MH_INVALID) {
-        const uint2 sp = key_sp[ph.key];
-        hit.shape = sp.x;
-        hit.prim = sp.y;
+        if (!KeyOnly) {
+            const uint2 sp = key_sp[ph.key];
+            hit.shape = sp.x;
+            hit.prim = sp.y;
+        }
         hit.t = ph.t;
         hit.u = ph.u;
         hit.v = ph.v;
@@ -1231,7 +1250,9 @@ MH_DEV V3 to_world(const SI &si, V3 v) {
 
 MH_DEV V3 vtx(const DScene &S, uint32_t i) { return ld3(S.positions + 3ull * i); }
 
-MH_DEV void compute_si(const DScene &S, const RayT &r, const Hit &h, SI &si) {
+// dp_du_out: where the frame's tangent goes before it is made orthogonal to
+// the shading normal (a per-primitive constant; the shade records keep it)
+MH_DEV void compute_si(const DScene &S, const RayT &r, const Hit &h, SI &si, V3 *dp_du_out = nullptr) {
     // single-exit form: every field is produced in registers and assigned once
     // (partial early-return initialisation made hipcc spill uv to scratch)
     const bool valid = h.shape != MH_INVALID;
@@ -1288,6 +1309,7 @@ MH_DEV void compute_si(const DScene &S, const RayT &r, const Hit &h, SI &si) {
         V3 tt;
         coordinate_system(sn, s, tt);
     }
+    if (dp_du_out) *dp_du_out = dp_du;
     si.valid = valid;
     si.shape = h.shape;
     si.p = p;
@@ -1298,6 +1320,102 @@ MH_DEV void compute_si(const DScene &S, const RayT &r, const Hit &h, SI &si) {
     si.uvx = uvx;
     si.uvy = uvy;
     si.wi = valid ? to_local(si, -r.d) : -r.d;
+}
+
+// What a fused bounce reads of the hit shape besides the interaction: its
+// emitter (MH_INVALID: none), whether its bsdf is diffuse, and then that
+// bsdf's reflectance texture.
+struct ShadeIds {
+    uint32_t emitter, tex;
+    bool smooth;
+};
+
+// compute_si and the id lookups from the hit key's shade record (srec: the LDS
+// copy, four 16-byte words per key; h: packet_batch<.., KeyOnly>'s hit).  p, uv
+// and wi are computed as in compute_si; n, s, t_ are the record's, which hold
+// compute_si's own bits.  A lane whose record has no constant frame (a mesh
+// with vertex normals) interpolates its shading normal and builds the frame
+// from it and the record's dp_du with compute_si's operations.
+MH_DEV void compute_si_rec(const DScene &S, const uint4 *srec, const RayT &r, const Hit &h, SI &si, ShadeIds &id) {
+    const bool valid = h.key != MH_INVALID;
+    V3 p = v3(0, 0, 0), n = v3(0, 0, 0), sn = v3(0, 0, 0), s = v3(0, 0, 0), t_ = v3(0, 0, 0);
+    float uvx = 0.f, uvy = 0.f;
+    uint32_t shape = MH_INVALID, flags = kSrConst;
+    id.emitter = MH_INVALID;
+    id.tex = 0u;
+    if (valid) {
+        const uint4 *q = srec + 4u * h.key;
+        const uint4 a = q[0], b = q[1], c = q[2], d = q[3];
+        n = sn = v3(__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z));
+        s = v3(__uint_as_float(a.w), __uint_as_float(b.x), __uint_as_float(b.y));
+        t_ = v3(__uint_as_float(b.z), __uint_as_float(b.w), __uint_as_float(c.x));
+        shape = c.y;
+        id.emitter = d.x;
+        id.tex = d.y;
+        flags = d.z;
+        if (flags & kSrRect) {
+            p = fma3s(r.d, h.t, r.o);
+            uvx = __builtin_fmaf(h.u, 0.5f, 0.5f);
+            uvy = __builtin_fmaf(h.v, 0.5f, 0.5f);
+        } else {
+            // the face and the mesh's first vertex from the record: no trip through shapes[]
+            const uint32_t *fi = S.faces + 3u * d.w;
+            const uint32_t vo = flags >> kSrVertexShift;
+            const uint32_t i0 = vo + fi[0], i1 = vo + fi[1], i2 = vo + fi[2];
+            const V3 p0 = vtx(S, i0), p1 = vtx(S, i1), p2 = vtx(S, i2);
+            const float b1 = h.u, b2 = h.v, b0 = 1.f - b1 - b2;
+            p = fma3s(p0, b0, fma3s(p1, b1, p2 * b2));
+            uvx = b1;
+            uvy = b2;
+            if (flags & kSrTexcoords) {
+                const float *tc = S.texcoords;
+                const float u0x = tc[2ull * i0], u0y = tc[2ull * i0 + 1], u1x = tc[2ull * i1],
+                            u1y = tc[2ull * i1 + 1], u2x = tc[2ull * i2], u2y = tc[2ull * i2 + 1];
+                uvx = __builtin_fmaf(u2x, b2, __builtin_fmaf(u1x, b1, u0x * b0));
+                uvy = __builtin_fmaf(u2y, b2, __builtin_fmaf(u1y, b1, u0y * b0));
+            }
+            if (!(flags & kSrConst)) {  // the record's s slot holds dp_du
+                const V3 n0 = ld3(S.normals + 3ull * i0), n1 = ld3(S.normals + 3ull * i1),
+                         n2 = ld3(S.normals + 3ull * i2);
+                const V3 nn = fma3s(n2, b2, fma3s(n1, b1, n0 * b0));
+                const V3 dp_du = s;
+                sn = nn * rsqrt_(dot(nn, nn));
+                // initialize_sh_frame (interaction.h:245-255)
+                s = normalize(fma3s(sn, -dot(sn, dp_du), dp_du));
+                if (dp_du.x == 0.f && dp_du.y == 0.f && dp_du.z == 0.f) {
+                    V3 tt;
+                    coordinate_system(sn, s, tt);
+                }
+                t_ = cross(sn, s);
+            }
+        }
+    }
+    id.smooth = (flags & kSrDiffuse) != 0u;
+    si.valid = valid;
+    si.shape = shape;
+    si.p = p;
+    si.n = n;
+    si.sn = sn;
+    si.s = s;
+    si.t_ = t_;
+    si.uvx = uvx;
+    si.uvy = uvy;
+    si.wi = valid ? to_local(si, -r.d) : -r.d;
+}
+
+// the interaction and the ids of a fused bounce kernel's closest hit: from the
+// shade records, or (Rec = false: h carries shape and prim) the tables' chain
+template <bool Rec>
+MH_DEV void shade_si(const DScene &S, const uint4 *srec, const RayT &r, const Hit &h, SI &si, ShadeIds &id) {
+    if constexpr (Rec) {
+        compute_si_rec(S, srec, r, h, si, id);
+    } else {
+        compute_si(S, r, h, si);
+        id.emitter = si.valid ? S.shapes[si.shape].emitter : MH_INVALID;
+        const uint32_t b = si.valid ? S.shapes[si.shape].bsdf : MH_INVALID;
+        id.smooth = b != MH_INVALID && S.bsdf_type[b] == MH_BSDF_DIFFUSE;
+        id.tex = id.smooth ? S.bsdf_tex[b] : 0u;
+    }
 }
 
 // Interaction::offset_p / spawn_ray / spawn_ray_to (interaction.h:133-162)

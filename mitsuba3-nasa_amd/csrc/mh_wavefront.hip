@@ -176,16 +176,25 @@ MH_DEV uint32_t lane_id() { return threadIdx.x & 63u; }
 // (group: 0 / 1 k_wf_bounce generating / not, 2 / 3 k_wf_bounce_prb
 // generating / not; phases: 0 state load or ray generation, 1 closest-hit
 // packet trace, 2 shade, 3 compaction + state store, 4 shadow packet trace,
-// 5 tail (NEE charge, radiance out), 6 iterations, 7 block prologue; 8-11
-// spare).  A phase is charged with the waits that fall in it (a load issued
-// earlier is paid where its value is first used: the state loads issued
-// after the closest trace are paid in shade).  Read by mh_exp_bphase.
+// 5 tail (NEE charge, radiance out), 6 iterations, 7 block prologue, 8 the head
+// of shade -- the interaction and the emitter / bsdf / texture ids, ahead of
+// the emitter sample -- with the rest of shade staying in 2; 9-11 spare).  A
+// phase is charged with the waits that fall in it (a load issued earlier is
+// paid where its value is first used: the state loads issued after the
+// closest trace are paid in shade).  Read by mh_exp_bphase.
 #ifdef MH_EXP_BPHASE
 __device__ unsigned long long g_bph[4][12];
 static size_t g_prb_ring_lds = 0;  // dynamic LDS of the last rgb PRB bounce launches (mh_exp_prb_occupancy)
 #define MH_BPH_DECL uint64_t bph_t = __builtin_amdgcn_s_memtime(); uint64_t bph[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #define MH_BPH(k) do { const uint64_t _t = __builtin_amdgcn_s_memtime(); bph[k] += _t - bph_t; bph_t = _t; } while (0)
 #define MH_BPH_ITER() (bph[6] += 1)
+// the head of shade ends here: the empty asm makes the interaction and the ids live ahead of the timestamp
+#define MH_BPH_HEAD(si, id)                                                                              \
+    do {                                                                                                 \
+        asm volatile("" ::"v"(si.wi.x), "v"(si.wi.y), "v"(si.wi.z), "v"(si.p.x), "v"(si.p.y), "v"(si.p.z), \
+                     "v"(si.uvx), "v"(si.uvy), "v"(id.emitter), "v"(id.tex), "v"((uint32_t)id.smooth));  \
+        MH_BPH(8);                                                                                       \
+    } while (0)
 #define MH_BPH_FLUSH(grp)                                                                 \
     do {                                                                                  \
         if (lane_id() == 0)                                                               \
@@ -195,6 +204,7 @@ static size_t g_prb_ring_lds = 0;  // dynamic LDS of the last rgb PRB bounce lau
 #define MH_BPH_DECL
 #define MH_BPH(k) do {} while (0)
 #define MH_BPH_ITER() do {} while (0)
+#define MH_BPH_HEAD(si, id) do {} while (0)
 #define MH_BPH_FLUSH(grp) do {} while (0)
 #endif
 
@@ -504,6 +514,8 @@ k_wf_bounce(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value, uin
     MH_BPH_DECL
     float *recs = reinterpret_cast<float *>(reinterpret_cast<uint8_t *>(lds) + fused_pairs_offset(S0));
     stage_pair_records(S0, recs);  // made visible by stage_tables' barrier
+    const uint4 *srec = reinterpret_cast<const uint4 *>(reinterpret_cast<uint8_t *>(lds) + fused_shade_offset(S0));
+    if (MH_SHADE_REC) stage_shade_records(S0, const_cast<uint4 *>(srec));
     const DScene S = stage_tables(S0, lds);
     uint32_t *ws = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(lds) + S0.tab_bytes) +
                    (threadIdx.x >> 6) * S0.stack_size;
@@ -559,7 +571,7 @@ k_wf_bounce(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value, uin
             MH_GUARD(pid < plane, kGuardPlane);
         }
         MH_BPH(0);
-        const Hit h = packet_batch<false, true>(S0.nodes, S0.prims, S0.prim_pairs, S0.key_sp, ws, 1u, ray, has, recs, dscr);
+        const Hit h = packet_batch<false, true, true, MH_SHADE_REC != 0>(S0.nodes, S0.prims, S0.prim_pairs, S0.key_sp, ws, 1u, ray, has, recs, dscr);
         MH_BPH(1);
         if (has) {
             if (Gen) {
@@ -581,11 +593,13 @@ k_wf_bounce(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value, uin
             const bool prev_delta = depth == 0;
             rng.inc = Gen ? gen_inc : (((uint64_t)w.tea(cur)[j] << 1) | 1u);
             SI si;
-            compute_si(S, ray, h, si);
+            ShadeIds id;
+            shade_si<MH_SHADE_REC != 0>(S, srec, ray, h, si, id);
+            MH_BPH_HEAD(si, id);
 
             // ---- direct emission (path.cpp:158-174); a camera ray that escapes
             // with the environment hidden returns 0 (valid_ray, path.cpp:115, 256, 284)
-            const uint32_t em = si.valid ? S.shapes[si.shape].emitter : S.environment;
+            const uint32_t em = si.valid ? id.emitter : S.environment;
             const bool hidden = depth == 0 && !si.valid && in.hide_emitters;
             if (em != MH_INVALID && !hidden) {
                 float em_pdf = prev_delta ? 0.f : emitter_pdf_direction(S, em, si, prev_p);
@@ -597,8 +611,7 @@ k_wf_bounce(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value, uin
             if (Gen && alpha)  // valid_ray (path.cpp:115, 256): decided at the camera vertex
                 out[5 * plane + pid] = (si.valid || (!in.hide_emitters && S.environment != MH_INVALID)) ? 1.f : 0.f;
             const bool active_next = (depth + 1 < in.max_depth) && si.valid;
-            const uint32_t b = si.valid ? S.shapes[si.shape].bsdf : MH_INVALID;
-            const bool smooth = b != MH_INVALID && S.bsdf_type[b] == MH_BSDF_DIFFUSE;
+            const bool smooth = id.smooth;
             const bool active_em = active_next && smooth;
 
             // ---- emitter sampling (path.cpp:187-208); visibility below
@@ -623,7 +636,7 @@ k_wf_bounce(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value, uin
             V3 bsdf_val = v3(0, 0, 0), bsdf_weight = v3(0, 0, 0), bs_wo = v3(0, 0, 0);
             float bsdf_pdf = 0.f, bs_pdf = 0.f, bs_eta = 0.f;
             if (smooth) {
-                V3 rho = tex_eval(S, S.bsdf_tex[b], si.uvx, si.uvy);
+                V3 rho = tex_eval(S, id.tex, si.uvx, si.uvy);
                 diffuse_eval_pdf(rho, si.wi, wo, true, bsdf_val, bsdf_pdf);
                 bs_wo = square_to_cosine_hemisphere(s2x, s2y);
                 bs_pdf = kInvPi * bs_wo.z;
@@ -1267,6 +1280,8 @@ k_wf_bounce_prb(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value,
     MH_BPH_DECL
     float *recs = reinterpret_cast<float *>(reinterpret_cast<uint8_t *>(lds) + fused_pairs_offset(S0));
     stage_pair_records(S0, recs);  // made visible by stage_tables' barrier
+    const uint4 *srec = reinterpret_cast<const uint4 *>(reinterpret_cast<uint8_t *>(lds) + fused_shade_offset(S0));
+    if (MH_SHADE_REC) stage_shade_records(S0, const_cast<uint4 *>(srec));
     const DScene S = stage_tables(S0, lds);
     uint32_t *ws = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(lds) + S0.tab_bytes) +
                    (threadIdx.x >> 6) * S0.stack_size;
@@ -1335,7 +1350,7 @@ k_wf_bounce_prb(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value,
             MH_GUARD(pid < gen.n_total, kGuardPathId);
         }
         MH_BPH(0);
-        const Hit h = packet_batch<false, true>(S0.nodes, S0.prims, S0.prim_pairs, S0.key_sp, ws, 1u, ray, i < n, recs, dscr);
+        const Hit h = packet_batch<false, true, true, MH_SHADE_REC != 0>(S0.nodes, S0.prims, S0.prim_pairs, S0.key_sp, ws, 1u, ray, i < n, recs, dscr);
         MH_BPH(1);
         if (i < n) {
             if (Gen) {
@@ -1371,13 +1386,14 @@ k_wf_bounce_prb(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value,
             const float eta = 1.f;
             rng.inc = Gen ? gen_inc : (((uint64_t)q.tea(cur)[j] << 1) | 1u);
             SI si;
-            compute_si(S, ray, h, si);
-            const uint32_t b = si.valid ? S.shapes[si.shape].bsdf : MH_INVALID;
-            const bool smooth = b != MH_INVALID && S.bsdf_type[b] == MH_BSDF_DIFFUSE;
+            ShadeIds id;
+            shade_si<MH_SHADE_REC != 0>(S, srec, ray, h, si, id);
+            MH_BPH_HEAD(si, id);
+            const bool smooth = id.smooth;
             bool active_next = !(in.hide_emitters && depth == 0 && !si.valid);
 
             // ---- emission (prb.py:143-152): charged to the earlier vertices
-            const uint32_t em = si.valid ? S.shapes[si.shape].emitter : S.environment;
+            const uint32_t em = si.valid ? id.emitter : S.environment;
             if (em != MH_INVALID) {
                 float em_pdf = prev_delta ? 0.f : emitter_pdf_direction(S, em, si, prev_p);
                 float mis = mis_weight(prev_pdf, em_pdf);
@@ -1420,8 +1436,8 @@ k_wf_bounce_prb(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value,
                 }
             }
             V3 rho = v3(0, 0, 0);
-            if (smooth) rho = tex_eval(S, S.bsdf_tex[b], si.uvx, si.uvy);
-            const int32_t slot = smooth ? q.slot_of_tex[S.bsdf_tex[b]] : -1;
+            if (smooth) rho = tex_eval(S, id.tex, si.uvx, si.uvy);
+            const int32_t slot = smooth ? q.slot_of_tex[id.tex] : -1;
             if (Bm) {
                 // every bitmap slot (kMaxRgbParams + b) records; b rides in depth_v's bits 8+
                 bvtx = slot >= (int32_t)kMaxRgbParams && depth < bm.n_depth;
@@ -1638,6 +1654,8 @@ k_wf_bounce_fwd(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value,
     if (!block_has_stride_work(it, n)) return;
     float *recs = reinterpret_cast<float *>(reinterpret_cast<uint8_t *>(lds) + fused_pairs_offset(S0));
     stage_pair_records(S0, recs);  // made visible by stage_tables' barrier
+    const uint4 *srec = reinterpret_cast<const uint4 *>(reinterpret_cast<uint8_t *>(lds) + fused_shade_offset(S0));
+    if (MH_SHADE_REC) stage_shade_records(S0, const_cast<uint4 *>(srec));
     const DScene S = stage_tables(S0, lds);
     uint32_t *ws = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(lds) + S0.tab_bytes) +
                    (threadIdx.x >> 6) * S0.stack_size;
@@ -1683,7 +1701,7 @@ k_wf_bounce_fwd(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value,
                 ray.maxt = w.mt[cur][j];
             }
         }
-        const Hit h = packet_batch<false, true>(S0.nodes, S0.prims, S0.prim_pairs, S0.key_sp, ws, 1u, ray, i < n, recs, dscr);
+        const Hit h = packet_batch<false, true, true, MH_SHADE_REC != 0>(S0.nodes, S0.prims, S0.prim_pairs, S0.key_sp, ws, 1u, ray, i < n, recs, dscr);
         if (i < n) {
             if (Gen) {
                 beta = v3(1.f, 1.f, 1.f);
@@ -1702,11 +1720,11 @@ k_wf_bounce_fwd(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value,
             const float eta = 1.f;
             rng.inc = Gen ? gen_inc : (((uint64_t)q.tea(cur)[j] << 1) | 1u);
             SI si;
-            compute_si(S, ray, h, si);
-            const uint32_t b = si.valid ? S.shapes[si.shape].bsdf : MH_INVALID;
-            const bool smooth = b != MH_INVALID && S.bsdf_type[b] == MH_BSDF_DIFFUSE;
+            ShadeIds id;
+            shade_si<MH_SHADE_REC != 0>(S, srec, ray, h, si, id);
+            const bool smooth = id.smooth;
             bool active_next = !(in.hide_emitters && depth == 0 && !si.valid);
-            const uint32_t em = si.valid ? S.shapes[si.shape].emitter : S.environment;
+            const uint32_t em = si.valid ? id.emitter : S.environment;
             if (em != MH_INVALID) {
                 float em_pdf = prev_delta ? 0.f : emitter_pdf_direction(S, em, si, prev_p);
                 float mis = mis_weight(prev_pdf, em_pdf);
@@ -1740,9 +1758,9 @@ k_wf_bounce_fwd(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value,
                 }
             }
             V3 rho = v3(0, 0, 0);
-            if (smooth) rho = tex_eval(S, S.bsdf_tex[b], si.uvx, si.uvy);
-            const bool tvtx = smooth && tg.slot_of_tex[S.bsdf_tex[b]] >= 0;
-            const V3 t = tvtx ? tex_tangent(S, S.bsdf_tex[b], si.uvx, si.uvy, tg) : v3(0, 0, 0);
+            if (smooth) rho = tex_eval(S, id.tex, si.uvx, si.uvy);
+            const bool tvtx = smooth && tg.slot_of_tex[id.tex] >= 0;
+            const V3 t = tvtx ? tex_tangent(S, id.tex, si.uvx, si.uvy, tg) : v3(0, 0, 0);
             if (shadow) {  // as if unoccluded; applied after the visibility test
                 V3 wo_em = to_local(si, ds.d);
                 V3 bsdf_value_em;
@@ -2222,6 +2240,53 @@ hipError_t launch_wavefront_prb(const DScene &S, const IntegratorParams &in, con
 }
 
 bool wf_fused(const DScene &S) { return variant::wf_fused(variant_facts(S)); }
+
+// The shade records of a scene (ShadeRec), one thread per scene-order key:
+// compute_si itself on a synthetic hit of the primitive, in this translation
+// unit's floating-point settings, so the stored frame holds the bits the
+// per-hit code produces (a constant frame depends on neither the ray nor the
+// barycentrics; nor do n and dp_du of a triangle with vertex normals).
+__global__ void __launch_bounds__(64)
+k_build_shade_recs(DScene S, ShadeRec *out) {
+    const uint32_t key = blockIdx.x * blockDim.x + threadIdx.x;
+    if (key >= S.n_prims) return;
+    const uint2 sp = S.key_sp[key];
+    const DShape &sh = S.shapes[sp.x];
+    Hit h;
+    h.key = key;
+    h.shape = sp.x;
+    h.prim = sp.y;
+    h.t = 1.f;
+    h.u = h.v = 0.25f;
+    const RayT r{v3(0, 0, 0), v3(0, 0, 1), kFloatMax};
+    SI si;
+    V3 dp_du;
+    compute_si(S, r, h, si, &dp_du);
+    const bool rect = sh.type == MH_SHAPE_RECTANGLE;
+    const bool konst = rect || !sh.has_normals;
+    if (!konst) si.s = dp_du;  // the frame follows the interpolated normal: compute_si_rec builds it from dp_du
+    const bool diffuse = sh.bsdf != MH_INVALID && S.bsdf_type[sh.bsdf] == MH_BSDF_DIFFUSE;
+    ShadeRec rec;
+    rec.n[0] = si.n.x; rec.n[1] = si.n.y; rec.n[2] = si.n.z;
+    rec.s[0] = si.s.x; rec.s[1] = si.s.y; rec.s[2] = si.s.z;
+    rec.t[0] = si.t_.x; rec.t[1] = si.t_.y; rec.t[2] = si.t_.z;
+    rec.shape = sp.x;
+    rec.prim = sp.y;
+    rec.bsdf = sh.bsdf;
+    rec.emitter = sh.emitter;
+    rec.tex = diffuse ? S.bsdf_tex[sh.bsdf] : 0u;
+    rec.flags = (rect ? kSrRect : 0u) | (konst ? kSrConst : 0u) | (diffuse ? kSrDiffuse : 0u) |
+                (!rect && sh.has_texcoords ? kSrTexcoords : 0u) | (rect ? 0u : sh.vertex_offset << kSrVertexShift);
+    rec.face = rect ? 0u : sh.face_offset + sp.y;
+    out[key] = rec;
+}
+
+bool wf_shade_records() { return MH_SHADE_REC != 0; }
+hipError_t launch_build_shade_recs(const DScene &S, ShadeRec *out, hipStream_t st) {
+    if (S.n_prims == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_build_shade_recs, dim3((S.n_prims + 63u) / 64u), dim3(64), 0, st, S, out);
+    return hipGetLastError();
+}
 
 uint32_t wf_grid(uint32_t grid) { return std::max<uint32_t>(kSeg, grid / kSeg * kSeg); }
 // Workgroups of the wavefront kernels.  A wave's share of a queue is fixed

@@ -8,9 +8,10 @@ Runs bench.py's step (path forward + prb backward, cornell_box 512^2 @ 256)
 and prints, per kernel family and generating / not, the share of the waves'
 s_memtime cycles in each phase of a bounce iteration (64 paths per wave):
 state load (or ray generation), closest-hit packet trace, shade, compaction +
-state store, shadow packet trace, tail; plus cycles per iteration.  The
-instrumented kernels run somewhat slower than the release build; compare
-shares within one build."""
+state store, shadow packet trace, tail; plus cycles per iteration, and the
+head of shade (the interaction and the emitter / bsdf / texture ids, up to
+the emitter sample) as a share of shade.  The instrumented kernels run
+somewhat slower than the release build; compare shares within one build."""
 import argparse
 import ctypes as C
 import json
@@ -21,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "mitsuba3-nasa_amd")]
 
 PHASES = ["load/gen", "closest trace", "shade", "store", "shadow trace", "tail"]
-SLOTS = 12  # per group: the 6 phases, iterations, prologue, 4 spare
+SLOTS = 12  # per group: the 6 phases, iterations, prologue, the head of shade, 3 spare
 GROUPS = ["k_wf_bounce<Gen>", "k_wf_bounce", "k_wf_bounce_prb<Gen>", "k_wf_bounce_prb"]
 
 
@@ -55,6 +56,8 @@ def main():
     out = {}
     for g, name in enumerate(GROUPS):
         v = [buf[g * SLOTS + k] for k in range(SLOTS)]
+        head = v[8]
+        v[2] += head  # slot 2 holds shade after its head
         tot = sum(v[:6])
         if not tot:
             continue
@@ -63,8 +66,10 @@ def main():
         names, vals = PHASES, v[:6]
         for p, x in zip(names, vals):
             print(f"    {p:15s} {x / tot:6.3f}  {x / iters:8.0f} cycles/iteration")
+        print(f"    shade head      {head / max(1, v[2]):6.3f}  {head / iters:8.0f} cycles/iteration  (share of shade)")
         out[name] = {"iterations": iters, "cycles_per_iteration": tot / iters,
-                     "share": {p: x / tot for p, x in zip(names, vals)}}
+                     "share": {p: x / tot for p, x in zip(names, vals)},
+                     "shade_head_of_shade": head / max(1, v[2]), "shade_head_cycles": head / iters}
     # the rgb PRB bounce with its NEE ring: workgroups per CU at the dynamic LDS of the launches above
     occ = getattr(_abi.lib(), "mh_exp_prb_occupancy", None)
     if occ is not None:
