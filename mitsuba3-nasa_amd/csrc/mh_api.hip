@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <string>
 #include <thread>
@@ -1328,17 +1329,48 @@ static plan::Facts call_facts(const mh_scene *s, const mh_integrator &in, uint32
     return f;
 }
 
+// the argument checks mh_render, mh_render_backward and mh_render_forward share
+// (after their own NULL and integrator checks)
+static int check_call_args(const mh_scene *s, const mh_integrator *in, uint32_t spp, uint32_t flags, const char *api,
+                           bool accumulating_output) {
+    if (in->rr_depth == 0)
+        return set_error(MH_ERR_INVALID_ARGUMENT, "\"rr_depth\" must be set to a value greater than zero!");
+    if (spp == 0) return set_error(MH_ERR_INVALID_ARGUMENT, std::string(api) + ": spp must be > 0");
+    if (int rc = check_reduce_flags(s, flags, api, accumulating_output)) return rc;
+    return check_phase_tables(s, api);
+}
+
+// the scene's pool of timing events, grown to n
+static hipError_t grow_evpool(mh_scene *s, size_t n) {
+    while (s->evpool.size() < n) {
+        hipEvent_t e;
+        if (hipError_t err = hipEventCreate(&e)) return err;
+        s->evpool.push_back(e);
+    }
+    return hipSuccess;
+}
+
+// ctr[0] += closest rays, ctr[1] += shadow rays of n_blocks blocks of wavefront
+// queue counters (one per chunk and pass, ctr_words = wf_counter_words(n_bounces) each)
+static void fold_wf_counters(const std::vector<uint32_t> &wctr, size_t ctr_words, size_t n_blocks, uint32_t n_bounces,
+                             unsigned long long ctr[2]) {
+    const size_t per_bounce = ctr_words / (n_bounces + 1), nseg = per_bounce / 32;
+    for (size_t blk = 0; blk < n_blocks; ++blk)
+        for (uint32_t b = 0; b < n_bounces; ++b)
+            for (size_t sg = 0; sg < nseg; ++sg) {
+                const size_t o = ctr_words * blk + per_bounce * b + 32 * sg;
+                ctr[0] += wctr[o + 0];
+                ctr[1] += wctr[o + 1];
+            }
+}
+
 static int render_impl(mh_scene *s, const mh_integrator *in, uint32_t seed, uint32_t spp, uint32_t spp_begin,
               uint32_t spp_end, float *film_rgbw, uint32_t flags, mh_stats *stats) {
     ScopedPhase phase_("Render");
     if (!s || !in || !film_rgbw) return set_error(MH_ERR_INVALID_ARGUMENT, "mh_render: NULL argument");
     if (in->type > MH_INTEGRATOR_PRBVOLPATH)
         return set_error(MH_ERR_INVALID_ARGUMENT, "mh_render: unknown integrator");
-    if (in->rr_depth == 0)
-        return set_error(MH_ERR_INVALID_ARGUMENT, "\"rr_depth\" must be set to a value greater than zero!");
-    if (spp == 0) return set_error(MH_ERR_INVALID_ARGUMENT, "mh_render: spp must be > 0");
-    if (int rc = check_reduce_flags(s, flags, "mh_render", true)) return rc;
-    if (int rc = check_phase_tables(s, "mh_render")) return rc;
+    if (int rc = check_call_args(s, in, spp, flags, "mh_render", true)) return rc;
     double t_start = now_ms();
     if (stats) *stats = mh_stats{};
     Layout L;
@@ -1389,11 +1421,7 @@ static int render_impl(mh_scene *s, const mh_integrator *in, uint32_t seed, uint
     const size_t n_chunks = (size_t)plan.chunks.n_chunks;
     const uint32_t n_bounces = wavefront ? in->max_depth : 0;
     const size_t ev_per_chunk = 3 + 2 * n_bounces;  // integrator span, bounce spans, splat end
-    while (s->evpool.size() < ev_per_chunk * n_chunks) {
-        hipEvent_t e;
-        MH_HIP(hipEventCreate(&e));
-        s->evpool.push_back(e);
-    }
+    MH_HIP(grow_evpool(s, ev_per_chunk * n_chunks));
     const size_t ctr_words = wavefront ? wf_counter_words(n_bounces) : 0;  // per pass
     const size_t ctr_per_chunk = ctr_words * L.n_passes;
     const int cus = device_cus(s->device);
@@ -1503,17 +1531,7 @@ static int render_impl(mh_scene *s, const mh_integrator *in, uint32_t seed, uint
             trace_ms += ms;
         }
     }
-    if (wavefront) {
-        const size_t per_bounce = ctr_words / (n_bounces + 1), nseg = per_bounce / 32;
-        for (size_t c = 0; c < n_chunks; ++c)
-            for (uint32_t p = 0; p < L.n_passes; ++p)
-                for (uint32_t b = 0; b < n_bounces; ++b)
-                    for (size_t sg = 0; sg < nseg; ++sg) {
-                        const size_t o = ctr_per_chunk * c + ctr_words * p + per_bounce * b + 32 * sg;
-                        ctr[0] += wctr[o + 0];
-                        ctr[1] += wctr[o + 1];
-                    }
-    }
+    if (wavefront) fold_wf_counters(wctr, ctr_words, n_chunks * L.n_passes, n_bounces, ctr);
     if (sched && vw_debug)  // MH_EXP_VSCNT builds: wave trips per phase
         if (int rc2 = print_vs_phases(s)) return rc2;
     if (volwave && !sched && vw_debug) {  // per-round queue sizes (+ MH_EXP_VWCNT builds: trips / steps)
@@ -1663,178 +1681,84 @@ static int prb_weights_impl(mh_scene *s, uint32_t seed, uint32_t spp, uint32_t s
 }
 
 // ---------------------------------------------------------------------------
-// Differentiated parameters -> slots: small slots 0..n_rgb-1 (register
-// accumulators): rgb textures, medium albedo, homogeneous sigma_t; large
-// slots (global atomics / tangent arrays): bitmaps, grids; an emitter's
-// radiance is a small slot too (emitter_slot)
+// Differentiated parameters -> slots, their buffers and the meta block: the
+// assignment and every layout are mh_slots.hpp's (host only); here they meet
+// the scene and the device
 // ---------------------------------------------------------------------------
-struct Slots {
-    std::vector<int32_t> slot_of_tex, sigma_slot, albedo_slot, emitter_slot, phase_slot;
-    std::vector<uint32_t> is_rgb;
-    std::vector<size_t> counts;
-    std::vector<uint32_t> slot_of_param;
-    uint32_t n_rgb = 0, n_bmp = 0, n_medium_params = 0, n_emitter_params = 0, n_phase_params = 0, bmp_tex = 0;
-    uint32_t grid_res[kMaxParams][3] = {};  // large sigma_t slots: the grid's resolution (x, y, z)
-    std::vector<float *> corner;            // their corner blocks (upload_slots, corners = true)
-    bool fx = false;                        // the blocks hold int64 fixed point (deterministic)
-    std::vector<uint8_t> meta;  // host image of the meta block (uploaded by upload_slots when it changed)
-};
+using slots::Slots;
 
 static int build_slots(const mh_scene *s, uint32_t n_params, const uint32_t *param_tex, bool vol, const char *api,
                        const char *method, Slots &P) {
-    const std::string a(api), m(method);
-    P.slot_of_tex.assign(std::max<uint32_t>(s->n_textures, 1), -1);
-    P.sigma_slot.assign(std::max<uint32_t>(s->n_media, 1), -1);
-    P.albedo_slot = P.sigma_slot;
-    P.phase_slot = P.sigma_slot;
-    P.emitter_slot.assign(std::max<size_t>(s->h_emitters.size(), 1), -1);
-    P.is_rgb.assign(kMaxParams, 0);
-    P.counts.assign(kMaxParams, 0);
-    P.slot_of_param.assign(n_params, 0);
-    for (uint32_t k = 0; k < n_params; ++k) {
-        const uint32_t kind = param_tex[k] & MH_PARAM_KIND_MASK, idx = param_tex[k] & ~MH_PARAM_KIND_MASK;
-        int32_t *owner;
-        bool small;
-        size_t cnt;
-        if (kind == 0) {
-            if (idx >= s->n_textures) return set_error(MH_ERR_INVALID_ARGUMENT, a + ": texture index out of bounds");
-            const DTexture &tx = s->h_textures[idx];
-            owner = &P.slot_of_tex[idx];
-            small = tx.type == MH_TEX_RGB;
-            cnt = small ? 3 : (size_t)tx.width * tx.height * tx.channels;
-        } else if (kind == MH_PARAM_MEDIUM_SIGMA_T || kind == MH_PARAM_MEDIUM_ALBEDO) {
-            if (!vol)
-                return set_error(MH_ERR_UNSUPPORTED, m + "(): medium parameters require the 'prbvolpath' integrator");
-            if (idx >= s->n_media) return set_error(MH_ERR_INVALID_ARGUMENT, a + ": medium index out of bounds");
-            const mh_medium &md = s->h_media[idx];
-            ++P.n_medium_params;
-            if (kind == MH_PARAM_MEDIUM_ALBEDO) {
-                owner = &P.albedo_slot[idx]; small = true; cnt = 3;
-            } else {
-                owner = &P.sigma_slot[idx];
-                small = md.type == MH_MEDIUM_HOMOGENEOUS;
-                cnt = small ? 1 : (size_t)md.grid_res[0] * md.grid_res[1] * md.grid_res[2];
-            }
-        } else if (kind == MH_PARAM_MEDIUM_PHASE_G) {
-            if (!vol)
-                return set_error(MH_ERR_UNSUPPORTED, m + "(): medium parameters require the 'prbvolpath' integrator");
-            if (idx >= s->n_media) return set_error(MH_ERR_INVALID_ARGUMENT, a + ": medium index out of bounds");
-            if (s->h_dmedia[idx].phase != MH_PHASE_HG)
-                return set_error(MH_ERR_UNSUPPORTED, m + "(): MH_PARAM_MEDIUM_PHASE_G needs a medium whose phase function "
-                                                         "is MH_PHASE_HG (other phase functions' parameters are not "
-                                                         "differentiable)");
-            ++P.n_medium_params;
-            ++P.n_phase_params;
-            owner = &P.phase_slot[idx]; small = true; cnt = 1;
-        } else if (kind == MH_PARAM_EMITTER_RADIANCE) {
-            if (idx >= s->h_emitters.size()) return set_error(MH_ERR_INVALID_ARGUMENT, a + ": emitter index out of bounds");
-            ++P.n_emitter_params;
-            owner = &P.emitter_slot[idx]; small = true; cnt = 3;
-        } else {
-            return set_error(MH_ERR_INVALID_ARGUMENT, a + ": unknown parameter kind");
-        }
-        if (*owner >= 0) return set_error(MH_ERR_INVALID_ARGUMENT, a + ": duplicate parameter");
-        int slot;
-        if (small) {
-            if (P.n_rgb >= (uint32_t)kMaxRgbParams) return set_error(MH_ERR_UNSUPPORTED, a + ": too many rgb parameters");
-            slot = (int)P.n_rgb++;
-            P.is_rgb[slot] = 1;
-        } else {
-            if (P.n_bmp >= (uint32_t)kMaxBitmapParams) return set_error(MH_ERR_UNSUPPORTED, a + ": too many bitmap parameters");
-            slot = kMaxRgbParams + (int)P.n_bmp++;
-            if (kind == 0) P.bmp_tex = idx;
-        }
-        P.counts[slot] = cnt;
-        if (kind == MH_PARAM_MEDIUM_SIGMA_T && !small)
-            for (int a = 0; a < 3; ++a) P.grid_res[slot][a] = s->h_media[idx].grid_res[a];
-        *owner = slot;
-        P.slot_of_param[k] = (uint32_t)slot;
+    slots::SceneFacts sc;
+    for (uint32_t t = 0; t < s->n_textures; ++t) {
+        const DTexture &tx = s->h_textures[t];
+        sc.textures.push_back({tx.type, (size_t)tx.width * tx.height * tx.channels});
     }
-    return MH_OK;
+    for (uint32_t m = 0; m < s->n_media; ++m) {
+        const mh_medium &md = s->h_media[m];
+        sc.media.push_back({md.type, {md.grid_res[0], md.grid_res[1], md.grid_res[2]}, s->h_dmedia[m].phase == MH_PHASE_HG});
+    }
+    sc.n_emitters = s->h_emitters.size();
+    const slots::Error err = slots::build_slots(sc, n_params, param_tex, vol, api, method, P);
+    return err ? set_error(err.code, err.msg) : MH_OK;
 }
 
-// per-slot device buffers (s->tmp_c, zeroed) and the meta block
-// slot_of_tex | is_rgb | bufs | sigma_slot | albedo_slot phase_slot | corner | emitter_slot (s->grad_meta)
+// per-slot device buffers (s->tmp_c, zeroed: blk = slots::slot_block(P.counts)) and the meta block (s->grad_meta)
 // corners: the grid sigma_t slots scatter into per-cell corner blocks
 // (s->grid_corner, zeroed; launch_corner_gather after the backward) unless
-// MH_GRID_CORNER=0, the block would exceed 16 GiB or cannot be allocated
+// MH_GRID_CORNER=0, the block would exceed its limits (slots::corner_layout) or cannot be allocated
 // fx: MH_FLAG_DETERMINISTIC -- int64 corner blocks (twice the bytes), which
 // are then required (no direct-atomic fallback)
-static hipError_t upload_slots(mh_scene *s, Slots &P, hipStream_t st, std::vector<float *> &bufs, GradArgs &ga,
-                               bool corners = false, bool fx = false) {
-    size_t total = 0;
-    std::vector<size_t> off(kMaxParams, 0);
-    for (int k = 0; k < kMaxParams; ++k) { off[k] = total; total += (P.counts[k] + 3) / 4 * 4; }
-    hipError_t e = s->tmp_c.alloc(std::max<size_t>(total, 1) * 4);
+static hipError_t upload_slots(mh_scene *s, Slots &P, const slots::SlotBlock &blk, hipStream_t st,
+                               std::vector<float *> &bufs, GradArgs &ga, bool corners = false, bool fx = false) {
+    hipError_t e = s->tmp_c.alloc(blk.alloc_floats() * 4);
     if (e != hipSuccess) return e;
-    e = hipMemsetAsync(s->tmp_c.ptr, 0, std::max<size_t>(total, 1) * 4, st);
+    e = hipMemsetAsync(s->tmp_c.ptr, 0, blk.alloc_floats() * 4, st);
     if (e != hipSuccess) return e;
     bufs.assign(kMaxParams, nullptr);
-    for (int k = 0; k < kMaxParams; ++k) bufs[k] = P.counts[k] ? s->tmp_c.as<float>() + off[k] : nullptr;
+    for (int k = 0; k < kMaxParams; ++k) bufs[k] = P.counts[k] ? s->tmp_c.as<float>() + blk.off[k] : nullptr;
     P.corner.assign(kMaxParams, nullptr);
     P.fx = false;
     if (corners && (fx || !env::grid_corner_off())) {
-        std::vector<size_t> coff(kMaxParams, 0);
-        std::vector<bool> use(kMaxParams, false);
-        size_t cfl = 0;
-        for (int k = 0; k < kMaxParams; ++k) {
-            const uint32_t *r = P.grid_res[k];
-            use[k] = r[0] && (uint64_t)(r[0] + 1) * (r[1] + 1) * (r[2] + 1) < (1ull << 32);
-            coff[k] = cfl;
-            if (use[k]) cfl += corner_floats(r);
-        }
-        const size_t eb = fx ? 8 : 4;  // bytes per corner value
-        if (cfl && cfl * eb <= (32ull << 30) && (fx || cfl * 4 <= (16ull << 30)) &&
-            s->grid_corner.alloc(cfl * eb) == hipSuccess) {
-            e = hipMemsetAsync(s->grid_corner.ptr, 0, cfl * eb, st);
+        const slots::CornerLayout C = slots::corner_layout(P.grid_res, fx);
+        if (C.fits && s->grid_corner.alloc(C.bytes()) == hipSuccess) {
+            e = hipMemsetAsync(s->grid_corner.ptr, 0, C.bytes(), st);
             if (e != hipSuccess) return e;
             for (int k = 0; k < kMaxParams; ++k)
-                if (use[k]) P.corner[k] = reinterpret_cast<float *>(s->grid_corner.as<uint8_t>() + coff[k] * eb);
+                if (C.use[k])
+                    P.corner[k] = reinterpret_cast<float *>(s->grid_corner.as<uint8_t>() + C.off[k] * C.value_bytes);
             P.fx = fx;
         } else {
             (void)hipGetLastError();
         }
     }
-    auto al16 = [](size_t x) { return (x + 15) / 16 * 16; };
-    const size_t o_slot = 0, o_isrgb = al16(P.slot_of_tex.size() * 4), o_bufs = al16(o_isrgb + kMaxParams * 4),
-                 o_sig = al16(o_bufs + kMaxParams * 8), o_alb = al16(o_sig + P.sigma_slot.size() * 4),
-                 o_ph = o_alb + P.albedo_slot.size() * 4,  // phase_slot: straight after albedo_slot (phase_g_backward)
-                 o_cor = al16(o_ph + P.phase_slot.size() * 4), o_em = al16(o_cor + kMaxParams * 8),
-                 meta_bytes = al16(o_em + P.emitter_slot.size() * 4);
-    std::vector<uint8_t> &meta = P.meta;
-    meta.assign(meta_bytes, 0);
-    memcpy(meta.data() + o_slot, P.slot_of_tex.data(), P.slot_of_tex.size() * 4);
-    memcpy(meta.data() + o_isrgb, P.is_rgb.data(), kMaxParams * 4);
-    memcpy(meta.data() + o_bufs, bufs.data(), kMaxParams * 8);
-    memcpy(meta.data() + o_sig, P.sigma_slot.data(), P.sigma_slot.size() * 4);
-    memcpy(meta.data() + o_alb, P.albedo_slot.data(), P.albedo_slot.size() * 4);
-    memcpy(meta.data() + o_cor, P.corner.data(), kMaxParams * 8);
-    memcpy(meta.data() + o_em, P.emitter_slot.data(), P.emitter_slot.size() * 4);
-    memcpy(meta.data() + o_ph, P.phase_slot.data(), P.phase_slot.size() * 4);
+    const slots::MetaLayout o = slots::meta_layout(s->n_textures, s->n_media, s->h_emitters.size());
+    if (!o.contracts_hold(s->n_media, P.n_emitter_params)) return hipErrorInvalidValue;
+    P.meta = slots::meta_image(o, P, bufs.data());
     // uploaded only when it changes (a new parameter set or reallocated slot
     // buffers), then with a stream sync; repeated calls with the same
     // parameters stay asynchronous
-    if (!(s->grad_meta.ptr && s->meta_host == meta)) {
-        e = s->grad_meta.alloc(meta_bytes);
+    if (!(s->grad_meta.ptr && s->meta_host == P.meta)) {
+        e = s->grad_meta.alloc(o.size);
         if (e != hipSuccess) return e;
-        e = hipMemcpyAsync(s->grad_meta.ptr, meta.data(), meta_bytes, hipMemcpyHostToDevice, st);
+        e = hipMemcpyAsync(s->grad_meta.ptr, P.meta.data(), o.size, hipMemcpyHostToDevice, st);
         if (e != hipSuccess) return e;
         e = hipStreamSynchronize(st);
         if (e != hipSuccess) return e;
-        s->meta_host = meta;
+        s->meta_host = P.meta;
     }
     const uint8_t *mb = s->grad_meta.as<uint8_t>();
-    ga.slot_of_tex = reinterpret_cast<const int32_t *>(mb + o_slot);
-    ga.is_rgb = reinterpret_cast<const uint32_t *>(mb + o_isrgb);
-    ga.bufs = reinterpret_cast<float *const *>(mb + o_bufs);
+    ga.slot_of_tex = reinterpret_cast<const int32_t *>(mb + o.slot);
+    ga.is_rgb = reinterpret_cast<const uint32_t *>(mb + o.is_rgb);
+    ga.bufs = reinterpret_cast<float *const *>(mb + o.bufs);
     ga.n_rgb = P.n_rgb;
-    ga.sigma_slot = P.n_medium_params ? reinterpret_cast<const int32_t *>(mb + o_sig) : nullptr;
-    ga.albedo_slot = P.n_medium_params ? reinterpret_cast<const int32_t *>(mb + o_alb) : nullptr;
-    ga.emitter_off = P.n_emitter_params ? (uint32_t)(o_em - o_slot) : 0u;
+    ga.sigma_slot = P.n_medium_params ? reinterpret_cast<const int32_t *>(mb + o.sigma) : nullptr;
+    ga.albedo_slot = P.n_medium_params ? reinterpret_cast<const int32_t *>(mb + o.albedo) : nullptr;
+    ga.emitter_off = o.emitter_off(P.n_emitter_params);
     ga.n_phase_g = P.n_phase_params;
     bool any_corner = false;
     for (float *c : P.corner) any_corner = any_corner || c;
-    ga.corner = any_corner ? reinterpret_cast<float *const *>(mb + o_cor) : nullptr;
+    ga.corner = any_corner ? reinterpret_cast<float *const *>(mb + o.corner) : nullptr;
     ga.hot_med = ga.hot_sigma = ga.hot_albedo = -1;
     ga.hot_buf = ga.hot_corner = nullptr;
     for (size_t m = 0; m < P.sigma_slot.size() && P.n_medium_params; ++m) {
@@ -1851,67 +1775,73 @@ static hipError_t upload_slots(mh_scene *s, Slots &P, hipStream_t st, std::vecto
     return hipSuccess;
 }
 
-static int render_backward_impl(mh_scene *s, const mh_integrator *in, uint32_t seed, uint32_t spp,
-                       uint32_t spp_begin, uint32_t spp_end, const float *grad_in,
-                       const float *weights, uint32_t n_params, const uint32_t *param_tex,
-                       float *const *grads, uint32_t flags, mh_stats *stats) {
-    ScopedPhase phase_("RenderBackward");
+// ---------------------------------------------------------------------------
+// mh_render_backward: render_backward_impl drives the steps below, which share
+// one BwdCall.  Every step enqueues on the scene's stream in the order written.
+// ---------------------------------------------------------------------------
+struct BwdCall {
+    mh_scene *s = nullptr;
+    const mh_integrator *in = nullptr;
+    uint32_t seed = 0, flags = 0;
+    hipStream_t st = nullptr;
+    Layout L{};
+    uint64_t n_px = 0, n = 0;  // pixels, samples of the slab
+    uint32_t S_ = 0;           // the slab's samples per pixel
+    bool dev = false, vol = false;  // MH_FLAG_DEVICE_POINTERS, prbvolpath
+    Slots P;
+    slots::SlotBlock blk;
+    std::vector<float *> bufs;  // slot -> its buffer in s->tmp_c
+    GradArgs ga;
+    plan::BackwardPlan plan;
+    const float *g_in = nullptr, *w = nullptr;  // grad_in (then grad_in / W per pixel) and W on the device
+    // what the engines leave for the finish and the stats
+    size_t wf_ctr_words = 0, wf_chunks = 0;
+    uint32_t *pvb_lost = nullptr;  // prbvolpath on the scheduler: overflow entries that found their list full
+    slots::FxScales fxs;           // deterministic: 2^S / 2^-S of the fixed point (fx_between)
+};
+
+// the call's waits (MH_WAIT, under the driver's name whichever step waits)
+static int bwd_wait(const BwdCall &c) {
+    if (wants_reduce(c.flags) && c.s->comm) return comm_wait(c.s->comm, c.st, "render_backward_impl");
+    MH_HIP(hipStreamSynchronize(c.st));
+    return MH_OK;
+}
+
+static int bwd_validate(const mh_scene *s, const mh_integrator *in, uint32_t spp, const float *grad_in,
+                        uint32_t n_params, const uint32_t *param_tex, float *const *grads, uint32_t flags) {
     if (!s || !in || !grad_in || (n_params && (!param_tex || !grads)))
         return set_error(MH_ERR_INVALID_ARGUMENT, "mh_render_backward: NULL argument");
     if (in->type != MH_INTEGRATOR_PRB && in->type != MH_INTEGRATOR_PRBVOLPATH)
         return set_error(MH_ERR_UNSUPPORTED, "render_backward(): requires the 'prb' or 'prbvolpath' integrator");
-    const bool vol = in->type == MH_INTEGRATOR_PRBVOLPATH;
-    if (in->rr_depth == 0)
-        return set_error(MH_ERR_INVALID_ARGUMENT, "\"rr_depth\" must be set to a value greater than zero!");
-    if (spp == 0) return set_error(MH_ERR_INVALID_ARGUMENT, "mh_render_backward: spp must be > 0");
-    if (int rc = check_reduce_flags(s, flags, "mh_render_backward", false)) return rc;
-    if (int rc = check_phase_tables(s, "mh_render_backward")) return rc;
-    double t_start = now_ms();
-    if (stats) *stats = mh_stats{};
-    Layout L;
-    int rc = make_layout(s, spp, spp_begin, spp_end, L, true);
-    if (rc) return rc;
-    MH_HIP(hipSetDevice(s->device));
-    g_call_issued = true;  // past argument validation: a failure from here aborts the communicator
-    hipStream_t st = s->stream;
-    const uint64_t n_px = (uint64_t)L.W * L.H;
-    const bool dev = flags & MH_FLAG_DEVICE_POINTERS;
+    return check_call_args(s, in, spp, flags, "mh_render_backward", false);
+}
 
-    // ---- parameter slots ----
-    Slots P;
-    int rc_slots = build_slots(s, n_params, param_tex, vol, "mh_render_backward", "render_backward", P);
-    if (rc_slots) return rc_slots;
-    std::vector<float *> bufs;
-    GradArgs ga;
-    const std::vector<size_t> &counts = P.counts;
-    const std::vector<uint32_t> &slot_of_param = P.slot_of_param;
-    const uint32_t n_rgb = P.n_rgb, n_bmp = P.n_bmp;
-    const uint32_t S_ = L.s_end - L.s_begin;
-    // ---- the plan (mh_plan.hpp): engine, determinism, chunks and streams ----
-    plan::Facts facts = call_facts(s, *in, flags, n_px, S_);
-    facts.n_rgb = n_rgb;
-    facts.n_bmp = n_bmp;
-    facts.bmp_slot_bytes = (uint64_t)counts[kMaxRgbParams] * 4;
+// the parameter slots, the plan (mh_plan.hpp: engine, determinism, chunks and
+// streams), the slots' buffers and the kernels' GradArgs
+static int bwd_slots_and_plan(BwdCall &c, uint32_t n_params, const uint32_t *param_tex) {
+    mh_scene *s = c.s;
+    Slots &P = c.P;
+    if (int rc = build_slots(s, n_params, param_tex, c.vol, "mh_render_backward", "render_backward", P)) return rc;
+    c.blk = slots::slot_block(P.counts);
+    plan::Facts facts = call_facts(s, *c.in, c.flags, c.n_px, c.S_);
+    facts.n_rgb = P.n_rgb;
+    facts.n_bmp = P.n_bmp;
+    facts.bmp_slot_bytes = (uint64_t)P.counts[kMaxRgbParams] * 4;
     facts.n_phase_params = P.n_phase_params;
     // (several bitmaps: all with the same channel count, as the scatter's
     // transposed issue assumes)
-    {
-        uint32_t ch = 0;
-        for (uint32_t t = 0; t < (uint32_t)P.slot_of_tex.size(); ++t)
-            if (P.slot_of_tex[t] >= kMaxRgbParams) {
-                const uint32_t c = s->h_textures[t].channels;
-                facts.bmp_same_ch = facts.bmp_same_ch && (ch == 0 || ch == c);
-                ch = c;
-            }
-    }
-    const plan::BackwardPlan plan =
-        plan::plan_backward(facts, env::plan_env(vol ? env::Call::BackwardVol : env::Call::Backward));
-    const bool fused = plan.fused, bmp_wf = plan.bmp_wf, wavefront = plan.wavefront;
+    uint32_t ch = 0;
+    for (uint32_t t = 0; t < (uint32_t)P.slot_of_tex.size(); ++t)
+        if (P.slot_of_tex[t] >= kMaxRgbParams) {
+            const uint32_t tc = s->h_textures[t].channels;
+            facts.bmp_same_ch = facts.bmp_same_ch && (ch == 0 || ch == tc);
+            ch = tc;
+        }
+    c.plan = plan::plan_backward(facts, env::plan_env(c.vol ? env::Call::BackwardVol : env::Call::Backward));
     // MH_FLAG_DETERMINISTIC on prbvolpath (fx) or on prb's replay kernel
     // (det_replay): int64 fixed point in two passes
-    const bool fx = plan.fx, det_replay = plan.det_replay, fxr = plan.fxr;
-    MH_HIP(upload_slots(s, P, st, bufs, ga, vol, fx));
-    if (fx)
+    MH_HIP(upload_slots(s, P, c.blk, c.st, c.bufs, c.ga, c.vol, c.plan.fx));
+    if (c.plan.fx)
         for (int k = 0; k < kMaxParams; ++k)
             if (P.grid_res[k][0] && !P.corner[k])
                 return set_error(MH_ERR_OUT_OF_MEMORY,
@@ -1919,19 +1849,28 @@ static int render_backward_impl(mh_scene *s, const mh_integrator *in, uint32_t s
     // one bitmap parameter of <= 48 KiB: the replay kernel accumulates its
     // texel gradients per workgroup in LDS (k_prb_backward)
     // (MH_PRB_LDS_TEX=0: global atomics, the parity tests' cross-check)
-    if (plan.lds_tex) {
-        ga.lds_slot = kMaxRgbParams;
-        ga.lds_floats = (uint32_t)counts[kMaxRgbParams];
+    if (c.plan.lds_tex) {
+        c.ga.lds_slot = kMaxRgbParams;
+        c.ga.lds_floats = (uint32_t)P.counts[kMaxRgbParams];
     }
+    return MH_OK;
+}
 
-    // ---- grad_in / weights on the device ----
+// grad_in and the weights on the device, grad_in / W once per pixel (the
+// adjoint of develop), the call's counters and the deterministic replay's mirror
+static int bwd_stage_adjoint(BwdCall &c, const float *grad_in, const float *weights) {
+    mh_scene *s = c.s;
+    const hipStream_t st = c.st;
+    const Layout &L = c.L;
+    const uint64_t n_px = c.n_px;
+    const uint32_t flags = c.flags;
     const float *g_in = grad_in;
-    if (!dev) {
+    if (!c.dev) {
         MH_HIP(s->tmp_d.alloc(n_px * 12));
         MH_HIP(hipMemcpyAsync(s->tmp_d.ptr, grad_in, n_px * 12, hipMemcpyHostToDevice, st));
         g_in = s->tmp_d.as<float>();
     }
-    const float *w = weights;
+    c.w = weights;
     if (!weights) {
         MH_HIP(s->weights_tmp.alloc(n_px * 4));
         MH_HIP(hipMemsetAsync(s->weights_tmp.ptr, 0, n_px * 4, st));
@@ -1947,220 +1886,224 @@ static int render_backward_impl(mh_scene *s, const mh_integrator *in, uint32_t s
         LaneMap lmw = lane_map(Lall, 0);
         MH_SPLAT(s->S, lmw, kSplatWeights, fast_splat(L, s->S), (uint32_t)n_px, 1,
                  n_px * (Lall.s_end - Lall.s_begin), 0, nullptr, s->weights_tmp.as<float>(),
-                 s->S.sampler_seed + seed, L.spp_pp >= 4, st, nullptr, plan.determ, 0, n_px, nullptr);
+                 s->S.sampler_seed + c.seed, L.spp_pp >= 4, st, nullptr, c.plan.determ, 0, n_px, nullptr);
         if (slab_w)
             if (int rc = reduce_result(s, flags, s->weights_tmp.as<float>(), n_px, st, false)) return rc;
-        w = s->weights_tmp.as<float>();
-    } else if (!dev) {
+        c.w = s->weights_tmp.as<float>();
+    } else if (!c.dev) {
         MH_HIP(s->tmp_e.alloc(n_px * 4));
         MH_HIP(hipMemcpyAsync(s->tmp_e.ptr, weights, n_px * 4, hipMemcpyHostToDevice, st));
-        w = s->tmp_e.as<float>();
+        c.w = s->tmp_e.as<float>();
     }
 
     MH_HIP(hipMemsetAsync(s->counters.ptr, 0, 256, st));
-    // grad_in / W once per pixel (the adjoint of develop)
     MH_HIP(s->gw.alloc(n_px * 16));  // float4 per pixel (k_grad_over_w)
-    MH_HIP(launch_grad_over_w(n_px, g_in, w, s->gw.as<float>(), st));
-    g_in = s->gw.as<float>();
-    const uint64_t n = n_px * S_;
+    MH_HIP(launch_grad_over_w(n_px, g_in, c.w, s->gw.as<float>(), st));
+    c.g_in = s->gw.as<float>();
     // the deterministic replay: small slots through acc_add_fx, bitmap texels
     // through bmp_add_fx into an int64 mirror of the slot block (no LDS accumulator)
-    if (det_replay) {
-        size_t total = 0;
-        for (int k = 0; k < kMaxParams; ++k) total += (counts[k] + 3) / 4 * 4;
-        MH_HIP(s->replay_fx.alloc(std::max<size_t>(total, 1) * 8));
-        MH_HIP(hipMemsetAsync(s->replay_fx.ptr, 0, std::max<size_t>(total, 1) * 8, st));
-        ga.fx_i64 = s->replay_fx.as<long long>();
-        ga.fx_f32 = s->tmp_c.as<float>();
-        ga.lds_slot = -1;
+    if (c.plan.det_replay) {
+        MH_HIP(s->replay_fx.alloc(c.blk.alloc_floats() * 8));
+        MH_HIP(hipMemsetAsync(s->replay_fx.ptr, 0, c.blk.alloc_floats() * 8, st));
+        c.ga.fx_i64 = s->replay_fx.as<long long>();
+        c.ga.fx_f32 = s->tmp_c.as<float>();
+        c.ga.lds_slot = -1;
     }
-    size_t wf_ctr_words = 0, wf_chunks = 0;
-    uint32_t *pvb_lost = nullptr;  // prbvolpath on the scheduler: overflow entries that found their list full
-    double fx_inv = 1.0;           // deterministic grid gradient: 2^-S of the fixed point
-    double fx_small_inv[kMaxParams] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0};  // and of each slot
-    // between the two passes of the deterministic grid gradient: the scale
-    // from pass 1's largest |item|; pass 1's rgb-slot adds and counters go
-    // fx_word: u32 max[0] (grid) and max[1 + k] (small slot k), double
-    // scale[k] at byte 64, int64 sums[3 k + c] at byte 192 (acc_add_fx)
-    auto fx_exp = [](uint32_t bits) {  // 2^S with |item| * 2^S < 2^31
-        float mx;
-        memcpy(&mx, &bits, 4);
-        int ex = 0;
-        if (mx > 0.f && std::isfinite(mx)) (void)std::frexp(mx, &ex);  // mx < 2^ex
-        return 31 - ex;
-    };
-    auto fx_between = [&](GradArgs &gp) -> hipError_t {
-        uint32_t mb[1 + kMaxParams] = {};  // words 1 + k: slot k (small slots; bitmaps on the replay)
-        hipError_t e = hipMemcpyAsync(mb, s->fx_word.ptr, sizeof(mb), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = wait_stream(s, flags, st);
-        if (e != hipSuccess) return e;
-        const int S0 = fx_exp(mb[0]);
-        fx_inv = std::ldexp(1.0, -S0);
-        gp.fx_scale = std::ldexp(1.0, S0);
-        double sc[kMaxParams];
-        for (int k = 0; k < kMaxParams; ++k) {
-            fx_small_inv[k] = std::ldexp(1.0, -fx_exp(mb[1 + k]));
-            sc[k] = std::ldexp(1.0, fx_exp(mb[1 + k]));
-        }
-        e = hipMemcpyAsync(s->fx_word.as<uint8_t>() + 64, sc, sizeof(sc), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemsetAsync(s->fx_word.as<uint8_t>() + 192, 0, 8 * 3 * kMaxRgbParams, st);
-        size_t total = 0;
-        for (int k = 0; k < kMaxParams; ++k) total += (counts[k] + 3) / 4 * 4;
-        if (e == hipSuccess) e = hipMemsetAsync(s->tmp_c.ptr, 0, std::max<size_t>(total, 1) * 4, st);
-        if (e == hipSuccess) e = hipMemsetAsync(s->counters.ptr, 0, 256, st);
-        return e;
-    };
-    // after pass 2: the small slots' exact sums into their buffers (which
-    // pass 2 left at zero: acc_add_fx bypasses the register accumulators)
-    auto fx_small_fold = [&]() -> hipError_t {
-        long long w[3 * kMaxRgbParams];
-        hipError_t e = hipMemcpyAsync(w, s->fx_word.as<uint8_t>() + 192, sizeof(w), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = wait_stream(s, flags, st);
-        for (uint32_t k = 0; e == hipSuccess && k < n_rgb; ++k) {
-            float v[3];
-            for (int c = 0; c < 3; ++c) v[c] = (float)((double)w[3 * k + c] * fx_small_inv[k]);
-            e = hipMemcpyAsync(bufs[k], v, std::min<size_t>(3, (counts[k] + 3) / 4 * 4) * 4, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = wait_stream(s, flags, st);
-        }
-        return e;
-    };
-    MH_HIP(hipEventRecord(s->ev0, st));
-    if (wavefront) {
-        const int cus = device_cus(s->device);
-        const uint32_t n_depth = plan.n_depth, chunk_px = plan.chunks.chunk_px;
-        const bool two = plan.chunks.two;  // two-stream chunk pipeline (fork_stream)
-        // MH_FLAG_SHARED_DEVICE (another call runs beside this one) or the two
-        // chunk streams: the launches take a share of the CUs' slots (wf_blocks)
-        const uint32_t grid = wf_grid(wf_blocks(cus, two || (flags & MH_FLAG_SHARED_DEVICE) != 0));
-        const uint64_t cap = (uint64_t)chunk_px * S_;
-        const size_t n_chunks = (size_t)plan.chunks.n_chunks;
-        const uint32_t n_bounces = in->max_depth;
-        const size_t ctr_per_chunk = wf_counter_words(n_bounces);
-        MH_HIP(s->wf_ws.alloc(wf_workspace_bytes(cap)));
-        MH_HIP(s->wf_ws_prb.alloc(wf_prb_workspace_bytes(cap)));
-        if (two) {
-            MH_HIP(s->wf_ws2.alloc(wf_workspace_bytes(cap)));
-            MH_HIP(s->wf_ws_prb2.alloc(wf_prb_workspace_bytes(cap)));
-        }
-        WfBitmapArgs bmp;
-        if (bmp_wf) {
-            MH_HIP(s->wf_ws_bmp.alloc(wf_bmp_workspace_bytes(cap, n_depth)));
-            if (two) MH_HIP(s->wf_ws_bmp2.alloc(wf_bmp_workspace_bytes(cap, n_depth)));
-            int max_wg = 64 << 10, per_cu_lds = 160 << 10;
-            (void)hipDeviceGetAttribute(&max_wg, hipDeviceAttributeMaxSharedMemoryPerBlock, s->device);
-            (void)hipDeviceGetAttribute(&per_cu_lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, s->device);
-            bmp.ws = s->wf_ws_bmp.ptr;
-            bmp.n_depth = n_depth;
-            bmp.slot = kMaxRgbParams;
-            // every bitmap slot kMaxRgbParams + b: its texture and its offset in
-            // the bitmap slots' contiguous block of s->tmp_c (upload_slots)
-            size_t boff = 0;
-            for (int b = 0; b < kMaxBitmapParams; ++b) {
-                bmp.off[b] = (uint32_t)boff;
-                boff += (counts[kMaxRgbParams + b] + 3) / 4 * 4;
-            }
-            for (uint32_t t = 0; t < (uint32_t)P.slot_of_tex.size(); ++t)
-                if (P.slot_of_tex[t] >= kMaxRgbParams) bmp.tex[P.slot_of_tex[t] - kMaxRgbParams] = t;
-            bmp.grad = bufs[kMaxRgbParams];
-            bmp.n_floats = (uint32_t)boff;
-            bmp.lds_max = plan.bmp_lds ? (uint32_t)std::min(max_wg, 64 << 10) : 0u;
-            if (plan.determ) {  // fixed-point texel sums (k_wf_bitmap_scatter<false, Fx>)
-                MH_HIP(s->bmp_fx.alloc((size_t)bmp.n_floats * 8 + 256));
-                bmp.fx_word = s->bmp_fx.as<uint32_t>();
-                bmp.fx_acc = reinterpret_cast<unsigned long long *>(s->bmp_fx.as<uint8_t>() + 256);
-            }
-            bmp.n_rec = s->counters.as<unsigned long long>() + kCtrAuxItems;
-            bmp.wg_lds = (uint32_t)max_wg;
-            bmp.cu_lds = (uint32_t)per_cu_lds;
-            bmp.cus = (uint32_t)cus;
-        }
-        // MH_FLAG_DETERMINISTIC: rgb slots summed per path and reduced in a
-        // fixed order (WfDet); bitmap texels in int64 fixed point (bmp.fx_acc)
-        const bool det_grad = plan.det_grad;
-        if (det_grad) MH_HIP(s->wf_ws_det.alloc(wf_det_workspace_bytes(cap)));
-        MH_HIP(s->wf_ctr.alloc(ctr_per_chunk * n_chunks * 4));
-        const size_t partial_bytes = (size_t)grid * kMaxRgbParams * 3 * 4;
-        MH_HIP(s->wf_partial.alloc(partial_bytes));
-        MH_HIP(hipMemsetAsync(s->wf_partial.ptr, 0, partial_bytes, st));
-        if (two) {
-            MH_HIP(s->wf_partial2.alloc(partial_bytes));
-            MH_HIP(hipMemsetAsync(s->wf_partial2.ptr, 0, partial_bytes, st));
-        }
-        while (s->evpool.size() < 3 * n_chunks) {
-            hipEvent_t e;
-            MH_HIP(hipEventCreate(&e));
-            s->evpool.push_back(e);
-        }
-        DScene S2 = s->S;  // stream2's scene view: its own stack overflow columns (stream-engine scenes)
-        if (two && s->S.stack_ovf) {
-            MH_HIP(s->stack_ovf2.alloc(s->stack_ovf.bytes));
-            S2.stack_ovf = s->stack_ovf2.as<uint32_t>();
-        }
-        if (two) MH_HIP(fork_stream(s, st));
-        size_t chunk = 0;
-        for (uint64_t p0 = 0; p0 < n_px; p0 += chunk_px, ++chunk) {
-            const uint32_t npx = (uint32_t)std::min<uint64_t>(chunk_px, n_px - p0);
-            // the chunk's stream and buffers (two: odd chunks on stream2)
-            const bool odd = two && (chunk & 1);
-            WfBitmapArgs bc = bmp;
-            if (odd) bc.ws = s->wf_ws_bmp2.ptr;
-            MH_HIP(launch_wavefront_prb(odd ? S2 : s->S, *in, lane_map(L, (uint32_t)p0), s->S.sampler_seed + seed,
-                                        (uint64_t)npx * S_, L.spp_pp >= 4, g_in, w, ga.slot_of_tex, n_rgb,
-                                        (odd ? s->wf_ws2 : s->wf_ws).ptr, (odd ? s->wf_ws_prb2 : s->wf_ws_prb).ptr, cap,
-                                        s->wf_ctr.as<uint32_t>() + ctr_per_chunk * chunk, n_bounces, grid,
-                                        (odd ? s->wf_partial2 : s->wf_partial).as<float>(), odd ? s->stream2 : st,
-                                        &s->evpool[3 * chunk], bmp_wf ? &bc : nullptr,
-                                        det_grad ? s->wf_ws_det.ptr : nullptr, ga.emitter_off));
-        }
-        if (two) MH_HIP(join_stream(s, st));
-        MH_HIP(launch_wf_grad_reduce(s->wf_partial.as<float>(), grid, n_rgb, ga.bufs, st));
-        if (two) MH_HIP(launch_wf_grad_reduce(s->wf_partial2.as<float>(), grid, n_rgb, ga.bufs, st));
-        wf_ctr_words = ctr_per_chunk;
-        wf_chunks = n_chunks;
-    } else if (plan.pvp_log) {
-        // prbvolpath: persistent grid, one NEE-walk log per thread (NeeLog;
-        // MH_PVP_NEE_LOG=0: the NEE walks are replayed, the branches below);
-        // single pass (MainLog, main_cap entries per thread) unless
-        // MH_PVP_SINGLE=0, on the phase scheduler (k_vol_sched<PvBwdMachine>)
-        // unless MH_PVP_SCHED=0 (the per-sample kernel k_prbvol_backward)
-        const int cus = device_cus(s->device);
-        uint32_t main_cap = plan.main_cap;
-        const uint32_t cap = plan.nee_cap;
-        bool sched = plan.sched;
-        // the persistent grid (and with it both per-thread logs): the
-        // scheduler's, or k_prbvol_backward's shrunk to the work (a wave takes
-        // 64 samples per batch, so more threads than samples would only hold log space)
-        const uint32_t blocks = sched ? vs_blocks(cus)
-                                      : (uint32_t)std::max<uint64_t>(
-                                            1, std::min<uint64_t>((uint64_t)cus * kPvpBlocksPerCu, (n + 255) / 256));
-        // a log that cannot be allocated degrades the kernel instead of failing
-        // the call: no MainLog -> primal + adjoint replay per sample; no NeeLog
-        // either -> one thread per sample with the NEE walks replayed
-        bool nee_ok = s->pvp_log.alloc((size_t)blocks * 256 * cap * 16) == hipSuccess;
-        if (!nee_ok) { (void)hipGetLastError(); s->pvp_log.release(); }
-        if (main_cap && (!nee_ok || s->pvp_main.alloc((size_t)blocks * 256 * main_cap * 64) != hipSuccess)) {
-            (void)hipGetLastError();
-            s->pvp_main.release();
-            main_cap = 0;
-        }
-        // overflow lists of the scheduler (2 + kPvbWalkRec float4 per entry)
-        const uint32_t ovf_cap = (uint32_t)std::min<uint64_t>(n, 1ull << 26);
-        sched = sched && main_cap && nee_ok &&
-                s->pvp_ovf.alloc((size_t)ovf_cap * (2 + kPvbWalkRec) * 16 + 256) == hipSuccess;
-        // MH_FLAG_DETERMINISTIC with a grid: pass 1 finds the largest |item| of
-        // the grid scatter (nothing is accumulated that survives), pass 2 adds
-        // round(item * 2^S) as int64, S = 31 - ceil(log2 max): |item| <= 2^31, so
-        // up to 2^31 items sum without overflow, and the sums are exact
-        if (fx) MH_HIP(s->fx_word.alloc(512));
-        for (uint32_t pass = fx ? 1u : 0u; pass <= (fx ? 2u : 0u); ++pass) {
-        GradArgs gp = ga;
+    return MH_OK;
+}
+
+// ---- MH_FLAG_DETERMINISTIC off the wavefront: int64 fixed point in two passes ----
+// Pass 1 finds the largest |item| of the grid scatter and of every slot
+// (nothing is accumulated that survives), pass 2 adds round(item * 2^S) as
+// int64 with slots::fx_exp's S: the sums are exact, so their order is free.
+
+// between the passes: the scales from pass 1's maxima; pass 1's rgb-slot adds
+// and counters go
+static hipError_t fx_between(BwdCall &c, GradArgs &gp) {
+    mh_scene *s = c.s;
+    const hipStream_t st = c.st;
+    uint32_t mb[1 + kMaxParams] = {};  // words 1 + k: slot k (small slots; bitmaps on the replay)
+    hipError_t e = hipMemcpyAsync(mb, s->fx_word.as<uint8_t>() + kFxMaxOff, sizeof(mb), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = wait_stream(s, c.flags, st);
+    if (e != hipSuccess) return e;
+    c.fxs = slots::fx_scales(mb);
+    gp.fx_scale = c.fxs.scale;
+    e = hipMemcpyAsync(s->fx_word.as<uint8_t>() + kFxScaleOff, c.fxs.slot_scale, sizeof(c.fxs.slot_scale),
+                       hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(s->fx_word.as<uint8_t>() + kFxSumOff, 0, 8 * 3 * kMaxRgbParams, st);
+    if (e == hipSuccess) e = hipMemsetAsync(s->tmp_c.ptr, 0, c.blk.alloc_floats() * 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(s->counters.ptr, 0, 256, st);
+    return e;
+}
+// launch(gp) -> status enqueues one pass with the pass's GradArgs
+static int fx_two_pass(BwdCall &c, const std::function<int(const GradArgs &)> &launch) {
+    mh_scene *s = c.s;
+    MH_HIP(s->fx_word.alloc(kFxWordBytes));
+    MH_HIP(hipMemsetAsync(s->fx_word.ptr, 0, kFxScaleOff - kFxMaxOff, c.st));
+    GradArgs gp = c.ga;
+    gp.fx_max = s->fx_word.as<uint32_t>();
+    for (uint32_t pass = 1; pass <= 2; ++pass) {
         gp.fx_mode = pass;
-        gp.fx_max = fx ? s->fx_word.as<uint32_t>() : nullptr;
-        if (pass == 1) MH_HIP(hipMemsetAsync(s->fx_word.ptr, 0, 64, st));
-        if (pass == 2) MH_HIP(fx_between(gp));
+        if (pass == 2) MH_HIP(fx_between(c, gp));
+        if (int rc = launch(gp)) return rc;
+    }
+    return MH_OK;
+}
+// after pass 2: the small slots' exact sums into their buffers (which
+// pass 2 left at zero: acc_add_fx bypasses the register accumulators)
+static hipError_t fx_small_fold(BwdCall &c) {
+    mh_scene *s = c.s;
+    const hipStream_t st = c.st;
+    long long w[3 * kMaxRgbParams];
+    hipError_t e = hipMemcpyAsync(w, s->fx_word.as<uint8_t>() + kFxSumOff, sizeof(w), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = wait_stream(s, c.flags, st);
+    for (uint32_t k = 0; e == hipSuccess && k < c.P.n_rgb; ++k) {
+        float v[3];
+        for (int ch = 0; ch < 3; ++ch) v[ch] = (float)((double)w[3 * k + ch] * c.fxs.slot_inv[k]);
+        e = hipMemcpyAsync(c.bufs[k], v, std::min<size_t>(3, slots::padded(c.P.counts[k])) * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = wait_stream(s, c.flags, st);
+    }
+    return e;
+}
+
+// ---- the engines ----------------------------------------------------------------
+// prb on the fused wavefront: rgb slots as per-block partials, bitmap slots
+// through vertex records and a texel scatter per chunk
+static int bwd_wavefront(BwdCall &c) {
+    mh_scene *s = c.s;
+    const mh_integrator *in = c.in;
+    const hipStream_t st = c.st;
+    const Layout &L = c.L;
+    const plan::BackwardPlan &plan = c.plan;
+    const GradArgs &ga = c.ga;
+    const uint64_t n_px = c.n_px;
+    const uint32_t S_ = c.S_, n_rgb = c.P.n_rgb;
+    const bool bmp_wf = plan.bmp_wf;
+    const int cus = device_cus(s->device);
+    const uint32_t n_depth = plan.n_depth, chunk_px = plan.chunks.chunk_px;
+    const bool two = plan.chunks.two;  // two-stream chunk pipeline (fork_stream)
+    // MH_FLAG_SHARED_DEVICE (another call runs beside this one) or the two
+    // chunk streams: the launches take a share of the CUs' slots (wf_blocks)
+    const uint32_t grid = wf_grid(wf_blocks(cus, two || (c.flags & MH_FLAG_SHARED_DEVICE) != 0));
+    const uint64_t cap = (uint64_t)chunk_px * S_;
+    const size_t n_chunks = (size_t)plan.chunks.n_chunks;
+    const uint32_t n_bounces = in->max_depth;
+    const size_t ctr_per_chunk = wf_counter_words(n_bounces);
+    MH_HIP(s->wf_ws.alloc(wf_workspace_bytes(cap)));
+    MH_HIP(s->wf_ws_prb.alloc(wf_prb_workspace_bytes(cap)));
+    if (two) {
+        MH_HIP(s->wf_ws2.alloc(wf_workspace_bytes(cap)));
+        MH_HIP(s->wf_ws_prb2.alloc(wf_prb_workspace_bytes(cap)));
+    }
+    WfBitmapArgs bmp;
+    if (bmp_wf) {
+        MH_HIP(s->wf_ws_bmp.alloc(wf_bmp_workspace_bytes(cap, n_depth)));
+        if (two) MH_HIP(s->wf_ws_bmp2.alloc(wf_bmp_workspace_bytes(cap, n_depth)));
+        int max_wg = 64 << 10, per_cu_lds = 160 << 10;
+        (void)hipDeviceGetAttribute(&max_wg, hipDeviceAttributeMaxSharedMemoryPerBlock, s->device);
+        (void)hipDeviceGetAttribute(&per_cu_lds, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, s->device);
+        bmp.ws = s->wf_ws_bmp.ptr;
+        bmp.n_depth = n_depth;
+        bmp.slot = kMaxRgbParams;
+        // every bitmap slot kMaxRgbParams + b: its texture and its offset in
+        // the bitmap slots' contiguous block of s->tmp_c (slots::slot_block)
+        for (int b = 0; b < kMaxBitmapParams; ++b) bmp.off[b] = c.blk.bmp_off[b];
+        for (uint32_t t = 0; t < (uint32_t)c.P.slot_of_tex.size(); ++t)
+            if (c.P.slot_of_tex[t] >= kMaxRgbParams) bmp.tex[c.P.slot_of_tex[t] - kMaxRgbParams] = t;
+        bmp.grad = c.bufs[kMaxRgbParams];
+        bmp.n_floats = c.blk.bmp_floats;
+        bmp.lds_max = plan.bmp_lds ? (uint32_t)std::min(max_wg, 64 << 10) : 0u;
+        if (plan.determ) {  // fixed-point texel sums (k_wf_bitmap_scatter<false, Fx>)
+            MH_HIP(s->bmp_fx.alloc((size_t)bmp.n_floats * 8 + 256));
+            bmp.fx_word = s->bmp_fx.as<uint32_t>();
+            bmp.fx_acc = reinterpret_cast<unsigned long long *>(s->bmp_fx.as<uint8_t>() + 256);
+        }
+        bmp.n_rec = s->counters.as<unsigned long long>() + kCtrAuxItems;
+        bmp.wg_lds = (uint32_t)max_wg;
+        bmp.cu_lds = (uint32_t)per_cu_lds;
+        bmp.cus = (uint32_t)cus;
+    }
+    // MH_FLAG_DETERMINISTIC: rgb slots summed per path and reduced in a
+    // fixed order (WfDet); bitmap texels in int64 fixed point (bmp.fx_acc)
+    const bool det_grad = plan.det_grad;
+    if (det_grad) MH_HIP(s->wf_ws_det.alloc(wf_det_workspace_bytes(cap)));
+    MH_HIP(s->wf_ctr.alloc(ctr_per_chunk * n_chunks * 4));
+    const size_t partial_bytes = (size_t)grid * kMaxRgbParams * 3 * 4;
+    MH_HIP(s->wf_partial.alloc(partial_bytes));
+    MH_HIP(hipMemsetAsync(s->wf_partial.ptr, 0, partial_bytes, st));
+    if (two) {
+        MH_HIP(s->wf_partial2.alloc(partial_bytes));
+        MH_HIP(hipMemsetAsync(s->wf_partial2.ptr, 0, partial_bytes, st));
+    }
+    MH_HIP(grow_evpool(s, 3 * n_chunks));
+    DScene S2 = s->S;  // stream2's scene view: its own stack overflow columns (stream-engine scenes)
+    if (two && s->S.stack_ovf) {
+        MH_HIP(s->stack_ovf2.alloc(s->stack_ovf.bytes));
+        S2.stack_ovf = s->stack_ovf2.as<uint32_t>();
+    }
+    if (two) MH_HIP(fork_stream(s, st));
+    size_t chunk = 0;
+    for (uint64_t p0 = 0; p0 < n_px; p0 += chunk_px, ++chunk) {
+        const uint32_t npx = (uint32_t)std::min<uint64_t>(chunk_px, n_px - p0);
+        // the chunk's stream and buffers (two: odd chunks on stream2)
+        const bool odd = two && (chunk & 1);
+        WfBitmapArgs bc = bmp;
+        if (odd) bc.ws = s->wf_ws_bmp2.ptr;
+        MH_HIP(launch_wavefront_prb(odd ? S2 : s->S, *in, lane_map(L, (uint32_t)p0), s->S.sampler_seed + c.seed,
+                                    (uint64_t)npx * S_, L.spp_pp >= 4, c.g_in, c.w, ga.slot_of_tex, n_rgb,
+                                    (odd ? s->wf_ws2 : s->wf_ws).ptr, (odd ? s->wf_ws_prb2 : s->wf_ws_prb).ptr, cap,
+                                    s->wf_ctr.as<uint32_t>() + ctr_per_chunk * chunk, n_bounces, grid,
+                                    (odd ? s->wf_partial2 : s->wf_partial).as<float>(), odd ? s->stream2 : st,
+                                    &s->evpool[3 * chunk], bmp_wf ? &bc : nullptr,
+                                    det_grad ? s->wf_ws_det.ptr : nullptr, ga.emitter_off));
+    }
+    if (two) MH_HIP(join_stream(s, st));
+    MH_HIP(launch_wf_grad_reduce(s->wf_partial.as<float>(), grid, n_rgb, ga.bufs, st));
+    if (two) MH_HIP(launch_wf_grad_reduce(s->wf_partial2.as<float>(), grid, n_rgb, ga.bufs, st));
+    c.wf_ctr_words = ctr_per_chunk;
+    c.wf_chunks = n_chunks;
+    return MH_OK;
+}
+
+// prbvolpath: persistent grid, one NEE-walk log per thread (NeeLog;
+// MH_PVP_NEE_LOG=0: the NEE walks are replayed, bwd_replay);
+// single pass (MainLog, main_cap entries per thread) unless
+// MH_PVP_SINGLE=0, on the phase scheduler (k_vol_sched<PvBwdMachine>)
+// unless MH_PVP_SCHED=0 (the per-sample kernel k_prbvol_backward)
+static int bwd_pvp_log(BwdCall &c) {
+    mh_scene *s = c.s;
+    const mh_integrator *in = c.in;
+    const hipStream_t st = c.st;
+    const Layout &L = c.L;
+    const uint64_t n = c.n;
+    const int cus = device_cus(s->device);
+    uint32_t main_cap = c.plan.main_cap;
+    const uint32_t cap = c.plan.nee_cap;
+    bool sched = c.plan.sched;
+    // the persistent grid (and with it both per-thread logs): the
+    // scheduler's, or k_prbvol_backward's shrunk to the work (a wave takes
+    // 64 samples per batch, so more threads than samples would only hold log space)
+    const uint32_t blocks = sched ? vs_blocks(cus)
+                                  : (uint32_t)std::max<uint64_t>(
+                                        1, std::min<uint64_t>((uint64_t)cus * kPvpBlocksPerCu, (n + 255) / 256));
+    // a log that cannot be allocated degrades the kernel instead of failing
+    // the call: no MainLog -> primal + adjoint replay per sample; no NeeLog
+    // either -> one thread per sample with the NEE walks replayed
+    bool nee_ok = s->pvp_log.alloc((size_t)blocks * 256 * cap * 16) == hipSuccess;
+    if (!nee_ok) { (void)hipGetLastError(); s->pvp_log.release(); }
+    if (main_cap && (!nee_ok || s->pvp_main.alloc((size_t)blocks * 256 * main_cap * 64) != hipSuccess)) {
+        (void)hipGetLastError();
+        s->pvp_main.release();
+        main_cap = 0;
+    }
+    // overflow lists of the scheduler (2 + kPvbWalkRec float4 per entry)
+    const uint32_t ovf_cap = (uint32_t)std::min<uint64_t>(n, 1ull << 26);
+    sched = sched && main_cap && nee_ok &&
+            s->pvp_ovf.alloc((size_t)ovf_cap * (2 + kPvbWalkRec) * 16 + 256) == hipSuccess;
+    auto launch = [&](const GradArgs &gp) -> int {
         if (sched) {
             VsBwdArgs bw;
-            bw.grad_in = g_in;
+            bw.grad_in = c.g_in;
             bw.coalesce = L.spp_pp >= 4;
             bw.ga = gp;
             bw.main_log = s->pvp_main.as<float4>();
@@ -2172,135 +2115,175 @@ static int render_backward_impl(mh_scene *s, const mh_integrator *in, uint32_t s
             bw.ovf_count = reinterpret_cast<uint32_t *>(bw.ovf_walks + (size_t)kPvbWalkRec * ovf_cap);
             bw.ovf_cap = ovf_cap;
             MH_HIP(hipMemsetAsync(bw.ovf_count, 0, 16, st));
-            pvb_lost = bw.ovf_count + 2;
+            c.pvb_lost = bw.ovf_count + 2;
             const LaneMap lm0 = lane_map(L, 0);
-            MH_HIP(launch_vol_sched_bwd(s->S, *in, lm0, s->S.sampler_seed + seed, n, bw, blocks,
+            MH_HIP(launch_vol_sched_bwd(s->S, *in, lm0, s->S.sampler_seed + c.seed, n, bw, blocks,
                                         s->counters.as<unsigned long long>(), st));
-            MH_HIP(launch_vol_sched_bwd_replays(s->S, *in, lm0, s->S.sampler_seed + seed, n, bw,
+            MH_HIP(launch_vol_sched_bwd_replays(s->S, *in, lm0, s->S.sampler_seed + c.seed, n, bw,
                                                 s->counters.as<unsigned long long>(), st));
             if (env::vw_debug()) {
-                MH_WAIT(s, flags, st);
+                if (int rc = bwd_wait(c)) return rc;
                 if (int rc2 = print_vs_phases(s)) return rc2;
                 uint32_t oc[3];
                 MH_HIP(hipMemcpy(oc, bw.ovf_count, sizeof(oc), hipMemcpyDeviceToHost));
                 fprintf(stderr, "pvb overflow replays: %u paths, %u walks, %u lost\n", oc[0], oc[1], oc[2]);
             }
         } else {
-            MH_HIP(launch_prb_backward(s->S, *in, lane_map(L, 0), s->S.sampler_seed + seed, n, L.spp_pp >= 4,
-                                       g_in, w, gp, fused, s->counters.as<unsigned long long>(), st,
+            MH_HIP(launch_prb_backward(s->S, *in, lane_map(L, 0), s->S.sampler_seed + c.seed, n, L.spp_pp >= 4,
+                                       c.g_in, c.w, gp, c.plan.fused, s->counters.as<unsigned long long>(), st,
                                        nee_ok ? s->pvp_log.as<float4>() : nullptr, cap, blocks,
                                        s->counters.as<unsigned long long>() + kCtrPvpHead,
                                        main_cap ? s->pvp_main.as<float4>() : nullptr, main_cap));
         }
-        }  // passes
-    } else if (fxr) {  // deterministic: prbvolpath replaying its NEE walks (MH_PVP_NEE_LOG=0), or the prb replay
-        MH_HIP(s->fx_word.alloc(512));
-        MH_HIP(hipMemsetAsync(s->fx_word.ptr, 0, 64, st));
-        GradArgs gp = ga;
-        gp.fx_max = s->fx_word.as<uint32_t>();
-        for (uint32_t pass = 1; pass <= 2; ++pass) {
-            gp.fx_mode = pass;
-            if (pass == 2) MH_HIP(fx_between(gp));
-            MH_HIP(launch_prb_backward(s->S, *in, lane_map(L, 0), s->S.sampler_seed + seed, n, L.spp_pp >= 4,
-                                       g_in, w, gp, fused, s->counters.as<unsigned long long>(), st));
-        }
-    } else {
-        MH_HIP(launch_prb_backward(s->S, *in, lane_map(L, 0), s->S.sampler_seed + seed, n, L.spp_pp >= 4,
-                                   g_in, w, ga, fused, s->counters.as<unsigned long long>(), st));
-    }
-    if (fxr) MH_HIP(fx_small_fold());
-    if (det_replay)
+        return MH_OK;
+    };
+    return c.plan.fx ? fx_two_pass(c, launch) : launch(c.ga);
+}
+
+// the per-lane replay kernel (k_prb_backward; prbvolpath with MH_PVP_NEE_LOG=0:
+// its NEE walks replayed), deterministic (fxr) in two fixed-point passes
+static int bwd_replay(BwdCall &c) {
+    mh_scene *s = c.s;
+    const Layout &L = c.L;
+    auto launch = [&](const GradArgs &gp) -> int {
+        MH_HIP(launch_prb_backward(s->S, *c.in, lane_map(L, 0), s->S.sampler_seed + c.seed, c.n, L.spp_pp >= 4,
+                                   c.g_in, c.w, gp, c.plan.fused, s->counters.as<unsigned long long>(), c.st));
+        return MH_OK;
+    };
+    return c.plan.fxr ? fx_two_pass(c, launch) : launch(c.ga);
+}
+
+// ---- after the engine -----------------------------------------------------------
+// the fixed-point sums and the corner blocks into the slot buffers, the
+// reduction over the communicator, and the slot buffers into the caller's
+static int bwd_finish(BwdCall &c, uint32_t n_params, float *const *grads) {
+    mh_scene *s = c.s;
+    const hipStream_t st = c.st;
+    const Slots &P = c.P;
+    const std::vector<float *> &bufs = c.bufs;
+    if (c.plan.fxr) MH_HIP(fx_small_fold(c));
+    if (c.plan.det_replay)
         for (int k = kMaxRgbParams; k < kMaxParams; ++k)
-            if (counts[k])
+            if (P.counts[k])
                 MH_HIP(launch_fx_to_float(s->replay_fx.as<long long>() + (bufs[k] - s->tmp_c.as<float>()), bufs[k],
-                                          counts[k], fx_small_inv[k], st));
+                                          P.counts[k], c.fxs.slot_inv[k], st));
     for (int k = 0; k < kMaxParams; ++k) {
         if (!P.corner[k]) continue;
         if (P.fx)
             MH_HIP(launch_corner_gather_fx(reinterpret_cast<const long long *>(P.corner[k]), bufs[k], P.grid_res[k],
-                                           fx_inv, st));
+                                           c.fxs.inv, st));
         else
             MH_HIP(launch_corner_gather(P.corner[k], bufs[k], P.grid_res[k], st));
     }
     MH_HIP(hipEventRecord(s->ev1, st));
-    if (wants_reduce(flags)) {  // the slot buffers are one block of s->tmp_c (upload_slots)
-        size_t total = 0;
-        for (int k = 0; k < kMaxParams; ++k) total += (counts[k] + 3) / 4 * 4;
-        if (int rc = reduce_result(s, flags, s->tmp_c.as<float>(), total, st, false)) return rc;
-    }
+    // the slot buffers are one block of s->tmp_c (upload_slots)
+    if (int rc = reduce_result(s, c.flags, s->tmp_c.as<float>(), c.blk.total, st, false)) return rc;
     // accumulate into the caller's gradient buffers
     std::vector<float> host_tmp;
     for (uint32_t k = 0; k < n_params; ++k) {
-        uint32_t slot = slot_of_param[k];
-        size_t c = counts[slot];
-        if (dev) {
-            MH_HIP(launch_accumulate(grads[k], bufs[slot], c, st));
+        const uint32_t slot = P.slot_of_param[k];
+        const size_t cnt = P.counts[slot];
+        if (c.dev) {
+            MH_HIP(launch_accumulate(grads[k], bufs[slot], cnt, st));
         } else {
-            host_tmp.resize(c);
-            MH_HIP(hipMemcpyAsync(host_tmp.data(), bufs[slot], c * 4, hipMemcpyDeviceToHost, st));
-            MH_WAIT(s, flags, st);
-            for (size_t i = 0; i < c; ++i) grads[k][i] += host_tmp[i];
+            host_tmp.resize(cnt);
+            MH_HIP(hipMemcpyAsync(host_tmp.data(), bufs[slot], cnt * 4, hipMemcpyDeviceToHost, st));
+            if (int rc = bwd_wait(c)) return rc;
+            for (size_t i = 0; i < cnt; ++i) grads[k][i] += host_tmp[i];
         }
     }
-    if (async_call(flags, stats)) return MH_OK;  // gradients stay stream-ordered on the device
-    auto check_lost = [&]() -> int {  // (after a stream sync) an overflow replay that did not run fails the call
-        uint32_t lost = 0;
-        if (pvb_lost) MH_HIP(hipMemcpy(&lost, pvb_lost, 4, hipMemcpyDeviceToHost));
-        if (lost)
-            return set_error(MH_ERR_OUT_OF_MEMORY, "render_backward(): " + std::to_string(lost) +
-                                                       " prbvolpath overflow replays did not fit their list "
-                                                       "(MH_PVP_SCHED=0 runs the per-sample kernel)");
-        return MH_OK;
-    };
+    return MH_OK;
+}
+
+// (after a stream sync) an overflow replay that did not run fails the call
+static int bwd_check_lost(const BwdCall &c) {
+    uint32_t lost = 0;
+    if (c.pvb_lost) MH_HIP(hipMemcpy(&lost, c.pvb_lost, 4, hipMemcpyDeviceToHost));
+    if (lost)
+        return set_error(MH_ERR_OUT_OF_MEMORY, "render_backward(): " + std::to_string(lost) +
+                                                   " prbvolpath overflow replays did not fit their list "
+                                                   "(MH_PVP_SCHED=0 runs the per-sample kernel)");
+    return MH_OK;
+}
+
+// the call's sync, the lost-replay check and, if asked for, the ray counters and timings
+static int bwd_stats(BwdCall &c, mh_stats *stats, double t_start) {
+    mh_scene *s = c.s;
+    const mh_integrator *in = c.in;
+    const hipStream_t st = c.st;
+    const bool wavefront = c.plan.wavefront;
+    const size_t wf_chunks = c.wf_chunks;
     if (!stats) {
-        MH_WAIT(s, flags, st);
-        return check_lost();
+        if (int rc = bwd_wait(c)) return rc;
+        return bwd_check_lost(c);
     }
     unsigned long long ctr[2] = {0, 0}, n_rec = 0;
-    std::vector<uint32_t> wctr(wf_ctr_words * wf_chunks);
+    std::vector<uint32_t> wctr(c.wf_ctr_words * wf_chunks);
     if (wavefront) {
         MH_HIP(hipMemcpyAsync(wctr.data(), s->wf_ctr.ptr, wctr.size() * 4, hipMemcpyDeviceToHost, st));
         MH_HIP(hipMemcpyAsync(&n_rec, s->counters.as<unsigned long long>() + kCtrAuxItems, 8, hipMemcpyDeviceToHost, st));
     } else
         MH_HIP(hipMemcpyAsync(ctr, s->counters.ptr, sizeof(ctr), hipMemcpyDeviceToHost, st));
-    MH_WAIT(s, flags, st);
-    if (int rc_lost = check_lost()) return rc_lost;
-    if (wavefront) {
-        const size_t per_bounce = wf_ctr_words / (in->max_depth + 1), nseg = per_bounce / 32;
-        for (size_t c = 0; c < wf_chunks; ++c)
-            for (uint32_t b = 0; b < in->max_depth; ++b)
-                for (size_t sg = 0; sg < nseg; ++sg) {
-                    ctr[0] += wctr[wf_ctr_words * c + per_bounce * b + 32 * sg + 0];
-                    ctr[1] += wctr[wf_ctr_words * c + per_bounce * b + 32 * sg + 1];
-                }
+    if (int rc = bwd_wait(c)) return rc;
+    if (int rc_lost = bwd_check_lost(c)) return rc_lost;
+    if (wavefront) fold_wf_counters(wctr, c.wf_ctr_words, wf_chunks, in->max_depth, ctr);
+    float ms = 0.f, trace_ms = 0.f, scat_ms = 0.f;
+    MH_HIP(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    for (size_t ck = 0; wavefront && ck < wf_chunks; ++ck) {
+        float t = 0.f;
+        MH_HIP(hipEventElapsedTime(&t, s->evpool[3 * ck], s->evpool[3 * ck + 1]));
+        trace_ms += t;
+        MH_HIP(hipEventElapsedTime(&t, s->evpool[3 * ck + 1], s->evpool[3 * ck + 2]));
+        scat_ms += t;
     }
-    if (stats) {
-        float ms = 0.f, trace_ms = 0.f, scat_ms = 0.f;
-        MH_HIP(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-        for (size_t c = 0; wavefront && c < wf_chunks; ++c) {
-            float t = 0.f;
-            MH_HIP(hipEventElapsedTime(&t, s->evpool[3 * c], s->evpool[3 * c + 1]));
-            trace_ms += t;
-            MH_HIP(hipEventElapsedTime(&t, s->evpool[3 * c + 1], s->evpool[3 * c + 2]));
-            scat_ms += t;
-        }
-        if (bmp_wf) {  // the texel scatter: one launch per chunk
-            stats->aux_items = n_rec;
-            stats->ms_aux = scat_ms;
-            stats->n_aux_launches = wf_chunks;
-        }
-        // the bounce-kernel span (fused: k_wf_bounce_prb launches only)
-        stats->ms_trace = trace_ms;
-        stats->n_trace_launches = wavefront ? (uint64_t)wf_chunks * in->max_depth : 0;
-        stats->mode = wavefront ? 1u : 0u;
-        stats->samples = n;
-        stats->rays_closest = ctr[0];
-        stats->rays_shadow = ctr[1];
-        stats->bounces = ctr[0];
-        stats->ms_total = now_ms() - t_start;
-        stats->ms_kernel = ms;
+    if (c.plan.bmp_wf) {  // the texel scatter: one launch per chunk
+        stats->aux_items = n_rec;
+        stats->ms_aux = scat_ms;
+        stats->n_aux_launches = wf_chunks;
     }
+    // the bounce-kernel span (fused: k_wf_bounce_prb launches only)
+    stats->ms_trace = trace_ms;
+    stats->n_trace_launches = wavefront ? (uint64_t)wf_chunks * in->max_depth : 0;
+    stats->mode = wavefront ? 1u : 0u;
+    stats->samples = c.n;
+    stats->rays_closest = ctr[0];
+    stats->rays_shadow = ctr[1];
+    stats->bounces = ctr[0];
+    stats->ms_total = now_ms() - t_start;
+    stats->ms_kernel = ms;
     return MH_OK;
+}
+
+static int render_backward_impl(mh_scene *s, const mh_integrator *in, uint32_t seed, uint32_t spp,
+                       uint32_t spp_begin, uint32_t spp_end, const float *grad_in,
+                       const float *weights, uint32_t n_params, const uint32_t *param_tex,
+                       float *const *grads, uint32_t flags, mh_stats *stats) {
+    ScopedPhase phase_("RenderBackward");
+    if (int rc = bwd_validate(s, in, spp, grad_in, n_params, param_tex, grads, flags)) return rc;
+    const double t_start = now_ms();
+    if (stats) *stats = mh_stats{};
+    BwdCall c;
+    if (int rc = make_layout(s, spp, spp_begin, spp_end, c.L, true)) return rc;
+    MH_HIP(hipSetDevice(s->device));
+    g_call_issued = true;  // past argument validation: a failure from here aborts the communicator
+    c.s = s;
+    c.in = in;
+    c.seed = seed;
+    c.flags = flags;
+    c.st = s->stream;
+    c.n_px = (uint64_t)c.L.W * c.L.H;
+    c.S_ = c.L.s_end - c.L.s_begin;
+    c.n = c.n_px * c.S_;
+    c.dev = flags & MH_FLAG_DEVICE_POINTERS;
+    c.vol = in->type == MH_INTEGRATOR_PRBVOLPATH;
+    if (int rc = bwd_slots_and_plan(c, n_params, param_tex)) return rc;
+    if (int rc = bwd_stage_adjoint(c, grad_in, weights)) return rc;
+    MH_HIP(hipEventRecord(s->ev0, c.st));
+    // wavefront; prbvolpath with its logs; else the replay kernel
+    if (int rc = c.plan.wavefront ? bwd_wavefront(c) : c.plan.pvp_log ? bwd_pvp_log(c) : bwd_replay(c)) return rc;
+    if (int rc = bwd_finish(c, n_params, grads)) return rc;
+    if (async_call(flags, stats)) return MH_OK;  // gradients stay stream-ordered on the device
+    return bwd_stats(c, stats, t_start);
 }
 
 // ---------------------------------------------------------------------------
@@ -2314,11 +2297,7 @@ static int render_forward_impl(mh_scene *s, const mh_integrator *in, uint32_t se
         return set_error(MH_ERR_INVALID_ARGUMENT, "mh_render_forward: NULL argument");
     if (in->type != MH_INTEGRATOR_PRB && in->type != MH_INTEGRATOR_PRBVOLPATH)
         return set_error(MH_ERR_UNSUPPORTED, "render_forward(): requires the 'prb' or 'prbvolpath' integrator");
-    if (in->rr_depth == 0)
-        return set_error(MH_ERR_INVALID_ARGUMENT, "\"rr_depth\" must be set to a value greater than zero!");
-    if (spp == 0) return set_error(MH_ERR_INVALID_ARGUMENT, "mh_render_forward: spp must be > 0");
-    if (int rc = check_reduce_flags(s, flags, "mh_render_forward", true)) return rc;
-    if (int rc = check_phase_tables(s, "mh_render_forward")) return rc;
+    if (int rc = check_call_args(s, in, spp, flags, "mh_render_forward", true)) return rc;
     const double t_start = now_ms();
     if (stats) *stats = mh_stats{};
     Layout L;
@@ -2334,7 +2313,7 @@ static int render_forward_impl(mh_scene *s, const mh_integrator *in, uint32_t se
     if (rc) return rc;
     std::vector<float *> bufs;
     GradArgs ga;
-    MH_HIP(upload_slots(s, P, st, bufs, ga));  // zeroed slot buffers, here the tangents
+    MH_HIP(upload_slots(s, P, slots::slot_block(P.counts), st, bufs, ga));  // zeroed slot buffers, here the tangents
     for (uint32_t k = 0; k < n_params; ++k) {
         const uint32_t slot = P.slot_of_param[k];
         if (!tangents[k]) return set_error(MH_ERR_INVALID_ARGUMENT, "mh_render_forward: NULL tangent");

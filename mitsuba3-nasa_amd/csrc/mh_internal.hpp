@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/mitsuba_hip.h"
+#include "mh_slots.hpp"
 #include "mh_variant.hpp"
 
 namespace mh {
@@ -19,10 +20,6 @@ struct Prim;
 struct LaneMap;
 
 using IntegratorParams = mh_integrator;
-
-constexpr int kMaxRgbParams = 4;     // constant-albedo gradient slots (register accumulators)
-constexpr int kMaxBitmapParams = 4;  // bitmap gradient slots (global atomics)
-constexpr int kMaxParams = kMaxRgbParams + kMaxBitmapParams;
 
 struct GradArgs {
     const int32_t *slot_of_tex;  // device: texture -> slot or -1
@@ -196,8 +193,7 @@ uint64_t grid_bricked_size(const uint32_t res[3]);
 void grid_to_bricks(const float *src, const uint32_t res[3], float *dst);
 hipError_t launch_grid_to_bricks(const float *src, const uint32_t res[3], float *dst, hipStream_t st);
 hipError_t launch_accumulate(float *dst, const float *src, uint64_t n, hipStream_t st);  // dst += src
-// grid sigma_t gradient: per-cell corner block (GradArgs::corner) -> (z, y, x) gradient (+=)
-uint64_t corner_floats(const uint32_t res[3]);
+// grid sigma_t gradient: per-cell corner block (GradArgs::corner, corner_floats of mh_slots.hpp) -> (z, y, x) gradient (+=)
 hipError_t launch_corner_gather(const float *corner, float *grad, const uint32_t res[3], hipStream_t st);
 // the int64 fixed-point form (fx_mode 2): grad += (float)(exact integer sum / fx_scale)
 hipError_t launch_corner_gather_fx(const long long *corner, float *grad, const uint32_t res[3], double inv_scale,

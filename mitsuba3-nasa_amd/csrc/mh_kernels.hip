@@ -1255,10 +1255,6 @@ hipError_t launch_fx_to_float(const long long *fx, float *grad, uint64_t n, doub
     return hipGetLastError();
 }
 
-uint64_t corner_floats(const uint32_t res[3]) {
-    return (uint64_t)(res[0] + 1) * (res[1] + 1) * (res[2] + 1) * 8u;
-}
-
 hipError_t launch_corner_gather(const float *corner, float *grad, const uint32_t res[3], hipStream_t st) {
     const uint64_t n = (uint64_t)res[0] * res[1] * res[2];
     if (n == 0) return hipSuccess;

@@ -1910,7 +1910,7 @@ struct GradCtx {
 static_assert(kMaxRgbParams == 4, "GradCtx names four small-slot accumulators");
 // MH_FLAG_DETERMINISTIC on prbvolpath (GradCtx::fx_mode): the small slots go
 // to int64 fixed point like the grid; the words after fx_max hold the
-// per-slot scales (doubles at byte 64) and sums (int64 x 3 at byte 192)
+// per-slot scales (doubles at kFxScaleOff) and sums (int64 x 3 at kFxSumOff, mh_slots.hpp)
 // Pass 2 sums each wave's contributions in LDS (ds_add_u64: integer adds are
 // exact, so their order does not matter) and adds them to the global words
 // once per wave and component at the flush (flush_small_slots), instead of
@@ -1934,7 +1934,7 @@ MH_DEV void acc_add_fx(GradCtx &g, int32_t k, V3 a) {
         if (m > 0.f) atomicMax(fx_wave_max() + 1 + k, __float_as_uint(m));
         return;
     }
-    const double sc = reinterpret_cast<const double *>(reinterpret_cast<const uint8_t *>(g.fx_max) + 64)[k];
+    const double sc = reinterpret_cast<const double *>(reinterpret_cast<const uint8_t *>(g.fx_max) + kFxScaleOff)[k];
     unsigned long long *w = fx_wave_sums() + 3 * k;
     atomicAdd(w + 0, (unsigned long long)__double2ll_rn((double)a.x * sc));
     atomicAdd(w + 1, (unsigned long long)__double2ll_rn((double)a.y * sc));
@@ -1949,7 +1949,7 @@ MH_DEV void bmp_add_fx(const GradCtx &g, int32_t k, const float *dst, float v) {
         if (a > 0.f) atomicMax(fx_wave_max() + 1 + k, __float_as_uint(a));
         return;
     }
-    const double sc = reinterpret_cast<const double *>(reinterpret_cast<const uint8_t *>(g.fx_max) + 64)[k];
+    const double sc = reinterpret_cast<const double *>(reinterpret_cast<const uint8_t *>(g.fx_max) + kFxScaleOff)[k];
     gatomic_add(reinterpret_cast<unsigned long long *>(g.fx_i64 + (dst - g.fx_f32)),
               (unsigned long long)__double2ll_rn((double)v * sc));
 }
@@ -4093,7 +4093,7 @@ MH_DEV void flush_small_slots(GradCtx &g, const GradArgs &ga) {
         const uint32_t j = threadIdx.x & 63u;
         if (j < 3u * ga.n_rgb) {
             const unsigned long long v = fx_wave_sums()[j];
-            unsigned long long *w = reinterpret_cast<unsigned long long *>(reinterpret_cast<uint8_t *>(g.fx_max) + 192);
+            unsigned long long *w = reinterpret_cast<unsigned long long *>(reinterpret_cast<uint8_t *>(g.fx_max) + kFxSumOff);
             if (v) gatomic_add(w + j, v);
         }
         return;
