@@ -281,7 +281,9 @@ typedef struct mh_stats {
     double   ms_kernel;         /* device time of the dominant kernel (hipEvents, ms) */
     double   ms_trace;          /* wavefront: device time of all k_wf_trace (mode 1) / k_wf_bounce (mode 2) launches (ms);
                                    volpath on the phase scheduler (mode 3): its k_vol_sched launches */
-    uint64_t n_trace_launches;  /* wavefront: number of those launches */
+    uint64_t n_trace_launches;  /* wavefront: number of those launches, counted as bounces (chunks x passes x
+                                   bounces): mode 2's first launch of a `path` chunk may run the camera bounce
+                                   and the bounce after it (k_wf_bounce<Gen, Two>) and still counts as two */
     uint32_t mode;              /* 0 megakernel, 1 wavefront (trace/shade/shadow), 2 wavefront fused bounce kernel,
                                    3 volpath wavefront (main / walk rounds) */
     uint32_t invalid_samples;   /* samples with a non-finite or negative (< -1e-5) radiance channel: the

@@ -178,6 +178,31 @@ bool dispatch(const WfTrace &k, F &&f) {
                   among<kEngBvh2, kEngWide, kEngQuant, kEngWideC>(k.eng), flag(k.nr1));
 }
 
+// ---- k_wf_bounce<Gen, Two>: f(Gen, Two).  Gen: the launch generates the camera rays; Two: it also
+// runs the bounce after the camera bounce, a survivor's state parked in the wave's LDS slab in between.
+// The slab (kParkBytes per workgroup of four waves, 16 dwords per lane) lies behind the kernel's other
+// dynamic LDS, and the two together stay within kFuse01MaxLds: five workgroups on a CU's 160 KB, the
+// occupancy the bounce kernels' register budget targets.
+#ifndef MH_WF_FUSE01
+#define MH_WF_FUSE01 1  // 0: every bounce is a launch of its own (A/B builds)
+#endif
+constexpr uint32_t kParkDwords = 16, kParkBytes = 4u * 64u * kParkDwords * 4u, kFuse01MaxLds = 32768;
+struct BouncePath {
+    bool two;           // the first launch runs bounces 0 and 1
+    uint32_t next;      // the bounce the host loop goes on with; its queue is in
+    uint32_t next_buf;  // this ping-pong buffer, its length in counter block `next`
+};
+inline BouncePath bounce_path(const Facts &f, uint32_t max_depth, uint32_t fused_lds_bytes) {
+    const bool two = MH_WF_FUSE01 && wf_fused(f) && max_depth >= 2 && fused_lds_bytes + kParkBytes <= kFuse01MaxLds;
+    // bounce b reads buffer b & 1 and counter block b, and writes buffer (b + 1) & 1 and block b + 1
+    return two ? BouncePath{true, 2, 0} : BouncePath{false, 1, 1};
+}
+template <class F>
+bool bounce(bool first, bool two, F &&f) {
+    if (first && two) return select(f, among<true>(true), among<true>(true));
+    return select(f, flag(first), among<false>(false));
+}
+
 // ---- k_wf_bounce_prb<NR, Gen, Bm, Det, Em>: f(NR1, Gen, Bm, Det, Em).  NR1: at most one rgb slot
 // (NR = 1), else kMaxRgbParams; Gen: the first bounce generates the camera rays; then the bitmap
 // log, the deterministic workspace and the emitter slots present

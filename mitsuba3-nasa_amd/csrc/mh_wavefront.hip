@@ -174,7 +174,9 @@ MH_DEV uint32_t lane_id() { return threadIdx.x & 63u; }
 // Diagnostic build (-DMH_EXP_BPHASE): s_memtime cycles of the fused bounce
 // kernels' phases, summed per wave and added once per wave into g_bph[group]
 // (group: 0 / 1 k_wf_bounce generating / not, 2 / 3 k_wf_bounce_prb
-// generating / not; phases: 0 state load or ray generation, 1 closest-hit
+// generating / not; the two-bounce generating instance reports both its
+// trips into group 0, an iteration being one wave-iteration; phases: 0 state
+// load or ray generation, 1 closest-hit
 // packet trace, 2 shade, 3 compaction + state store, 4 shadow packet trace,
 // 5 tail (NEE charge, radiance out), 6 iterations, 7 block prologue, 8 the head
 // of shade -- the interaction and the emitter / bsdf / texture ids, ahead of
@@ -494,11 +496,32 @@ k_wf_shade(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value, uint
 // state and film position) in registers instead of reading them from the
 // queue -- the 80-B path state of every camera ray never goes to HBM.  Slot j
 // of bounce 0 is path j; n_total: paths of the chunk.
-template <bool Gen>
+// Two (with Gen; variant::bounce_path): the launch runs the camera bounce and
+// the bounce after it.  The cornell box is closed behind every camera ray and
+// Russian roulette starts later, so nearly every path survives bounce 0 and
+// the queue between the two bounces compacts nothing: slot j of bounce 1 is,
+// up to a few dead lanes, path j again.  A survivor of bounce 0 therefore
+// parks its state in the wave's LDS slab (behind the deferral scratch; the
+// launch adds variant::kParkBytes) instead of appending it to a queue in HBM,
+// and the wave runs the same bounce body a second time at depth 1, with holes
+// where lanes ended: its ray is read back before the closest-hit trace and
+// the rest after it, where the other launches read HBM.  pid and rng.inc stay
+// in registers, and so does L across the shadow trace; across a closest-hit
+// trace L waits in the slab, in the slots of the ray being traced (in
+// registers there it cost two more spilled VGPRs); maxt after spawn_ray is
+// kFloatMax.  The generating part writes the camera vertex's state to the
+// slab, so both trips read theirs from it.  The second trip's
+// survivors go to the queue of bounce 2 (`cur` is bounce 1's, ctr_next counter
+// block 2); the queue length of bounce 1 and its shadow rays are counted per
+// wave and added once to counter block 1, statistics as ctr[.. + 1].  A lane
+// reads only the slab column it wrote, so the slab needs no fence or barrier.
+constexpr uint32_t kParkFloats = variant::kParkDwords * 64u;  // per wave, field-major [field][64] as the NEE ring
+template <bool Gen, bool Two = false>
 __global__ void __launch_bounds__(256, MH_BOUNCE_WAVES)
 k_wf_bounce(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value, uint64_t plane, float *out,
             WfPacked w, int cur, uint32_t seg_cap, uint32_t *ctr, uint32_t *ctr_next, uint64_t n_total,
             uint64_t *carry, uint32_t pass, int alpha) {
+    static_assert(Gen || !Two, "the two-bounce instance generates its paths");
     extern __shared__ uint4 lds[];
     const SegIter it = seg_iter();
     auto seg_count = [&](uint32_t sg) -> uint32_t {
@@ -522,13 +545,20 @@ k_wf_bounce(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value, uin
     uint8_t *dscr = reinterpret_cast<uint8_t *>(lds) + fused_scratch_offset(S0) + (threadIdx.x >> 6) * kDeferScratch;
     const int nxt = cur ^ 1;
     uint32_t n_shadow = 0;
+    // Two: this lane's column of the wave's park slab (the wave index through readfirstlane: a scalar base),
+    // and bounce 1's queue length and shadow rays
+    float *park = nullptr;
+    if constexpr (Two)
+        park = reinterpret_cast<float *>(reinterpret_cast<uint8_t *>(lds) + fused_lds_bytes(S0)) +
+               __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * kParkFloats + lane_id();
+    uint32_t n_queue1 = 0, n_shadow1 = 0;
     MH_BPH(7);
     const uint32_t seg = it.seg;
     for (uint32_t base = it.wave * 64u; base < n; base += it.nwaves * 64u) {
         const uint32_t sbase = seg * seg_cap;
         MH_BPH_ITER();
         const uint32_t i = base + lane_id();
-        const bool has = i < n;
+        bool has = i < n;  // (Two, second trip: the lane survived bounce 0)
         const uint32_t j = sbase + i;
         MH_GUARD(!has || i < seg_cap, kGuardQueueSlot);
         bool alive = false, shadow = false;
@@ -558,6 +588,14 @@ k_wf_bounce(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value, uin
                 gen_inc = g.inc;  // the TEA of this lane, reused below
                 out[3 * plane + pid] = sx;
                 out[4 * plane + pid] = sy;
+                if constexpr (Two) {  // the camera vertex's state, where both trips read theirs
+                    park[0 * 64] = park[1 * 64] = park[2 * 64] = 0.f;  // L
+                    park[6 * 64] = park[7 * 64] = park[8 * 64] = 1.f;
+                    park[9 * 64] = park[10 * 64] = park[11 * 64] = 0.f;
+                    park[12 * 64] = 1.f;
+                    park[13 * 64] = __uint_as_float((uint32_t)gen_state);
+                    park[14 * 64] = __uint_as_float((uint32_t)(gen_state >> 32));
+                }
             } else {
                 const float4 q0 = w.pl(cur, 0)[j], q1 = w.pl(cur, 1)[j];
                 const uint32_t pd = __float_as_uint(q1.w);
@@ -571,127 +609,181 @@ k_wf_bounce(DScene S0, IntegratorParams in, LaneMap lm, uint32_t seed_value, uin
             MH_GUARD(pid < plane, kGuardPlane);
         }
         MH_BPH(0);
-        const Hit h = packet_batch<false, true, true, MH_SHADE_REC != 0>(S0.nodes, S0.prims, S0.prim_pairs, S0.key_sp, ws, 1u, ray, has, recs, dscr);
-        MH_BPH(1);
-        if (has) {
-            if (Gen) {
-                tp = v3(1.f, 1.f, 1.f);
-                L = v3(0.f, 0.f, 0.f);
-                prev_p = v3(0.f, 0.f, 0.f);
-                prev_pdf = 1.f;
-                rng.state = gen_state;
-            } else {
-                const uint32_t jl = j;
-                const float4 q2 = w.pl(cur, 2)[jl], q3 = w.pl(cur, 3)[jl], q4 = w.pl(cur, 4)[jl];
-                tp = v3(q2.x, q2.y, q2.z);
-                prev_pdf = q2.w;
-                prev_p = v3(q3.x, q3.y, q3.z);
-                L = v3(q4.x, q4.y, q4.z);
-                rng.state = (uint64_t)__float_as_uint(q3.w) | ((uint64_t)__float_as_uint(q4.w) << 32);
-            }
-            eta = 1.f;  // diffuse / null BSDFs: eta stays 1, only the camera vertex is delta
-            const bool prev_delta = depth == 0;
-            rng.inc = Gen ? gen_inc : (((uint64_t)w.tea(cur)[j] << 1) | 1u);
-            SI si;
-            ShadeIds id;
-            shade_si<MH_SHADE_REC != 0>(S, srec, ray, h, si, id);
-            MH_BPH_HEAD(si, id);
-
-            // ---- direct emission (path.cpp:158-174); a camera ray that escapes
-            // with the environment hidden returns 0 (valid_ray, path.cpp:115, 256, 284)
-            const uint32_t em = si.valid ? id.emitter : S.environment;
-            const bool hidden = depth == 0 && !si.valid && in.hide_emitters;
-            if (em != MH_INVALID && !hidden) {
-                float em_pdf = prev_delta ? 0.f : emitter_pdf_direction(S, em, si, prev_p);
-                float mis_bsdf = mis_weight(prev_pdf, em_pdf);
-                V3 le = v3(0, 0, 0);
-                if (prev_pdf > 0.f) le = emitter_eval(S, em, si);
-                L = fma3(tp, le * mis_bsdf, L);
-            }
-            if (Gen && alpha)  // valid_ray (path.cpp:115, 256): decided at the camera vertex
-                out[5 * plane + pid] = (si.valid || (!in.hide_emitters && S.environment != MH_INVALID)) ? 1.f : 0.f;
-            const bool active_next = (depth + 1 < in.max_depth) && si.valid;
-            const bool smooth = id.smooth;
-            const bool active_em = active_next && smooth;
-
-            // ---- emitter sampling (path.cpp:187-208); visibility below
-            float e0 = rng.next_float(), e1 = rng.next_float();
-            DirS ds;
-            ds.pdf = 0.f;
-            ds.d = v3(0, 0, 0);
-            ds.delta = false;
-            V3 em_weight = v3(0, 0, 0), wo = v3(0, 0, 0);
-            if (active_em) {
-                em_weight = scene_sample_emitter_direction(S, si.p, e0, e1, ds);
-                if (ds.pdf != 0.f && nonzero(em_weight)) {
-                    shadow = true;
-                    sray = spawn_ray_to(si.p, si.n, ds.p);
+        // one bounce of the wave's paths.  Two: the same body twice, `first` wave-uniform; kept a loop,
+        // since a peeled second copy of the body would double the code in every wave's loop
+        uint32_t trip = 0;
+#pragma nounroll
+        do {
+            const bool first = !Two || trip == 0;
+            const Hit h = packet_batch<false, true, true, MH_SHADE_REC != 0>(S0.nodes, S0.prims, S0.prim_pairs, S0.key_sp, ws, 1u, ray, has, recs, dscr);
+            MH_BPH(1);
+            if (has) {
+                if (Gen && !Two) {
+                    tp = v3(1.f, 1.f, 1.f);
+                    L = v3(0.f, 0.f, 0.f);
+                    prev_p = v3(0.f, 0.f, 0.f);
+                    prev_pdf = 1.f;
+                    rng.state = gen_state;
+                } else if (Two) {  // the camera vertex's or the parked survivor's
+                    L = v3(park[0 * 64], park[1 * 64], park[2 * 64]);
+                    tp = v3(park[6 * 64], park[7 * 64], park[8 * 64]);
+                    prev_p = v3(park[9 * 64], park[10 * 64], park[11 * 64]);
+                    prev_pdf = park[12 * 64];
+                    rng.state = (uint64_t)__float_as_uint(park[13 * 64]) | ((uint64_t)__float_as_uint(park[14 * 64]) << 32);
+                } else {
+                    const uint32_t jl = j;
+                    const float4 q2 = w.pl(cur, 2)[jl], q3 = w.pl(cur, 3)[jl], q4 = w.pl(cur, 4)[jl];
+                    tp = v3(q2.x, q2.y, q2.z);
+                    prev_pdf = q2.w;
+                    prev_p = v3(q3.x, q3.y, q3.z);
+                    L = v3(q4.x, q4.y, q4.z);
+                    rng.state = (uint64_t)__float_as_uint(q3.w) | ((uint64_t)__float_as_uint(q4.w) << 32);
                 }
-                wo = to_local(si, ds.d);
-            }
+                eta = 1.f;  // diffuse / null BSDFs: eta stays 1, only the camera vertex is delta
+                const bool prev_delta = depth == 0;
+                rng.inc = Gen ? gen_inc : (((uint64_t)w.tea(cur)[j] << 1) | 1u);
+                SI si;
+                ShadeIds id;
+                shade_si<MH_SHADE_REC != 0>(S, srec, ray, h, si, id);
+                MH_BPH_HEAD(si, id);
 
-            // ---- BSDF eval + sample (path.cpp:212-216)
-            (void)rng.next_float();
-            float s2x = rng.next_float(), s2y = rng.next_float();
-            V3 bsdf_val = v3(0, 0, 0), bsdf_weight = v3(0, 0, 0), bs_wo = v3(0, 0, 0);
-            float bsdf_pdf = 0.f, bs_pdf = 0.f, bs_eta = 0.f;
-            if (smooth) {
-                V3 rho = tex_eval(S, id.tex, si.uvx, si.uvy);
-                diffuse_eval_pdf(rho, si.wi, wo, true, bsdf_val, bsdf_pdf);
-                bs_wo = square_to_cosine_hemisphere(s2x, s2y);
-                bs_pdf = kInvPi * bs_wo.z;
-                bs_eta = 1.f;
-                bsdf_weight = (si.wi.z > 0.f && bs_pdf > 0.f) ? rho : v3(0, 0, 0);
-            }
-            if (shadow) {  // (path.cpp:220-230), applied below if unoccluded
-                a_nee = tp;
-                b_nee = (bsdf_val * em_weight) * (ds.delta ? 1.f : mis_weight(ds.pdf, bsdf_pdf));
-            }
+                // ---- direct emission (path.cpp:158-174); a camera ray that escapes
+                // with the environment hidden returns 0 (valid_ray, path.cpp:115, 256, 284)
+                const uint32_t em = si.valid ? id.emitter : S.environment;
+                const bool hidden = depth == 0 && !si.valid && in.hide_emitters;
+                if (em != MH_INVALID && !hidden) {
+                    float em_pdf = prev_delta ? 0.f : emitter_pdf_direction(S, em, si, prev_p);
+                    float mis_bsdf = mis_weight(prev_pdf, em_pdf);
+                    V3 le = v3(0, 0, 0);
+                    if (prev_pdf > 0.f) le = emitter_eval(S, em, si);
+                    L = fma3(tp, le * mis_bsdf, L);
+                }
+                if (Gen && first && alpha)  // valid_ray (path.cpp:115, 256): decided at the camera vertex
+                    out[5 * plane + pid] = (si.valid || (!in.hide_emitters && S.environment != MH_INVALID)) ? 1.f : 0.f;
+                const bool active_next = (depth + 1 < in.max_depth) && si.valid;
+                const bool smooth = id.smooth;
+                const bool active_em = active_next && smooth;
 
-            // ---- BSDF sampling, state update, Russian roulette (path.cpp:234-280)
-            ray = spawn_ray(si.p, si.n, to_world(si, bs_wo));
-            tp = tp * bsdf_weight;
-            eta *= bs_eta;
-            prev_p = si.p;
-            prev_pdf = bs_pdf;
-            if (si.valid) depth += 1;
-            float tmax = hmax(tp);
-            float rr_prob = fminf(tmax * (eta * eta), 0.95f);
-            bool rr_active = depth >= in.rr_depth;
-            bool rr_continue = rng.next_float() < rr_prob;
-            if (rr_active) tp = tp * rcp(rr_prob);
-            alive = active_next && (!rr_active || rr_continue) && tmax != 0.f;
-        }
-        MH_BPH(2);
-        // ---- compaction: the survivor's next-bounce state leaves registers
-        // before the shadow trace (only L and the NEE product stay live across it)
-        const uint32_t slot = sbase + wave_append(ctr_next + seg * 32, alive);
-        MH_GUARD(!alive || slot - sbase < seg_cap, kGuardAppendSlot);
-        const float rng_hi = __uint_as_float((uint32_t)(rng.state >> 32));
-        if (alive) {
-            w.pl(nxt, 0)[slot] = make_float4(ray.o.x, ray.o.y, ray.o.z, ray.maxt);
-            w.pl(nxt, 1)[slot] = make_float4(ray.d.x, ray.d.y, ray.d.z, __uint_as_float(pid | (depth << kPidBits)));
-            w.pl(nxt, 2)[slot] = make_float4(tp.x, tp.y, tp.z, prev_pdf);
-            w.pl(nxt, 3)[slot] = make_float4(prev_p.x, prev_p.y, prev_p.z, __uint_as_float((uint32_t)rng.state));
-            w.tea(nxt)[slot] = (uint32_t)(rng.inc >> 1);
-        } else if (has && carry) {
-            carry[pid] = rng.state;  // multi-pass: the next pass continues the stream
-        }
-        MH_BPH(3);
-        // ---- visibility of the NEE sample (scene.cpp:201-210)
-        const Hit sh = packet_batch<true, true>(S0.nodes, S0.prims, S0.prim_pairs, S0.key_sp, ws, 1u, sray, shadow, recs, dscr);
-        MH_BPH(4);
-        if (shadow && sh.shape == MH_INVALID) L = fma3(a_nee, b_nee, L);
-        n_shadow += (uint32_t)__popcll(__ballot(shadow));
-        // ---- radiance: survivors carry it on, finished paths -> sample planes
-        if (alive) {
-            w.pl(nxt, 4)[slot] = make_float4(L.x, L.y, L.z, rng_hi);
-        } else if (has) {
-            out[pid] = L.x; out[plane + pid] = L.y; out[2 * plane + pid] = L.z;
-        }
-        MH_BPH(5);
+                // ---- emitter sampling (path.cpp:187-208); visibility below
+                float e0 = rng.next_float(), e1 = rng.next_float();
+                DirS ds;
+                ds.pdf = 0.f;
+                ds.d = v3(0, 0, 0);
+                ds.delta = false;
+                V3 em_weight = v3(0, 0, 0), wo = v3(0, 0, 0);
+                if (active_em) {
+                    em_weight = scene_sample_emitter_direction(S, si.p, e0, e1, ds);
+                    if (ds.pdf != 0.f && nonzero(em_weight)) {
+                        shadow = true;
+                        sray = spawn_ray_to(si.p, si.n, ds.p);
+                    }
+                    wo = to_local(si, ds.d);
+                }
+
+                // ---- BSDF eval + sample (path.cpp:212-216)
+                (void)rng.next_float();
+                float s2x = rng.next_float(), s2y = rng.next_float();
+                V3 bsdf_val = v3(0, 0, 0), bsdf_weight = v3(0, 0, 0), bs_wo = v3(0, 0, 0);
+                float bsdf_pdf = 0.f, bs_pdf = 0.f, bs_eta = 0.f;
+                if (smooth) {
+                    V3 rho = tex_eval(S, id.tex, si.uvx, si.uvy);
+                    diffuse_eval_pdf(rho, si.wi, wo, true, bsdf_val, bsdf_pdf);
+                    bs_wo = square_to_cosine_hemisphere(s2x, s2y);
+                    bs_pdf = kInvPi * bs_wo.z;
+                    bs_eta = 1.f;
+                    bsdf_weight = (si.wi.z > 0.f && bs_pdf > 0.f) ? rho : v3(0, 0, 0);
+                }
+                if (shadow) {  // (path.cpp:220-230), applied below if unoccluded
+                    a_nee = tp;
+                    b_nee = (bsdf_val * em_weight) * (ds.delta ? 1.f : mis_weight(ds.pdf, bsdf_pdf));
+                }
+
+                // ---- BSDF sampling, state update, Russian roulette (path.cpp:234-280)
+                ray = spawn_ray(si.p, si.n, to_world(si, bs_wo));
+                tp = tp * bsdf_weight;
+                eta *= bs_eta;
+                prev_p = si.p;
+                prev_pdf = bs_pdf;
+                if (si.valid) depth += 1;
+                float tmax = hmax(tp);
+                float rr_prob = fminf(tmax * (eta * eta), 0.95f);
+                bool rr_active = depth >= in.rr_depth;
+                bool rr_continue = rng.next_float() < rr_prob;
+                if (rr_active) tp = tp * rcp(rr_prob);
+                alive = active_next && (!rr_active || rr_continue) && tmax != 0.f;
+            }
+            MH_BPH(2);
+            // ---- compaction: the survivor's next-bounce state leaves registers
+            // before the shadow trace (only L and the NEE product stay live across it)
+            // (Two, first trip: to the park slab, and the queue of bounce 1 is only counted)
+            const bool to_park = Two && first;
+            uint32_t slot = 0;
+            if (!to_park) {
+                slot = sbase + wave_append(ctr_next + seg * 32, alive);
+                MH_GUARD(!alive || slot - sbase < seg_cap, kGuardAppendSlot);
+            } else {
+                n_queue1 += (uint32_t)__popcll(__ballot(alive));
+            }
+            const float rng_hi = __uint_as_float((uint32_t)(rng.state >> 32));
+            if (alive && to_park) {
+                park[0 * 64] = ray.o.x; park[1 * 64] = ray.o.y; park[2 * 64] = ray.o.z;
+                park[3 * 64] = ray.d.x; park[4 * 64] = ray.d.y; park[5 * 64] = ray.d.z;
+                park[6 * 64] = tp.x; park[7 * 64] = tp.y; park[8 * 64] = tp.z;
+                park[9 * 64] = prev_p.x; park[10 * 64] = prev_p.y; park[11 * 64] = prev_p.z;
+                park[12 * 64] = prev_pdf;
+                park[13 * 64] = __uint_as_float((uint32_t)rng.state); park[14 * 64] = rng_hi;
+            } else if (alive) {
+                w.pl(nxt, 0)[slot] = make_float4(ray.o.x, ray.o.y, ray.o.z, ray.maxt);
+                w.pl(nxt, 1)[slot] = make_float4(ray.d.x, ray.d.y, ray.d.z, __uint_as_float(pid | (depth << kPidBits)));
+                w.pl(nxt, 2)[slot] = make_float4(tp.x, tp.y, tp.z, prev_pdf);
+                w.pl(nxt, 3)[slot] = make_float4(prev_p.x, prev_p.y, prev_p.z, __uint_as_float((uint32_t)rng.state));
+                w.tea(nxt)[slot] = (uint32_t)(rng.inc >> 1);
+            } else if (has && carry) {
+                uint32_t cp = pid;
+                // Two: the address is formed here; shared with the generating part's load of
+                // carry[pid] it lived in two VGPRs across both trips, and was spilled
+                if constexpr (Two) asm volatile("" : "+v"(cp));
+                carry[cp] = rng.state;  // multi-pass: the next pass continues the stream
+            }
+            MH_BPH(3);
+            // ---- visibility of the NEE sample (scene.cpp:201-210)
+            const Hit sh = packet_batch<true, true>(S0.nodes, S0.prims, S0.prim_pairs, S0.key_sp, ws, 1u, sray, shadow, recs, dscr);
+            MH_BPH(4);
+            if (shadow && sh.shape == MH_INVALID) L = fma3(a_nee, b_nee, L);
+            (first ? n_shadow : n_shadow1) += (uint32_t)__popcll(__ballot(shadow));
+            // ---- radiance: survivors carry it on (parked: in their registers), finished paths -> sample planes
+            if (alive) {
+                if (!to_park) w.pl(nxt, 4)[slot] = make_float4(L.x, L.y, L.z, rng_hi);
+            } else if (has) {
+                out[pid] = L.x; out[plane + pid] = L.y; out[2 * plane + pid] = L.z;
+            }
+            MH_BPH(5);
+            if constexpr (Two) {
+                // bounce 1 of the survivors, skipped when the wave has none.  What the second
+                // trip does not read is made dead across its closest-hit trace.
+                has = alive;
+                trip = first && __ballot(has) != 0 ? 1u : 2u;
+                ray = sray = RayT{v3(0, 0, 0), v3(0, 0, 1), -1.f};
+                if (trip == 1u && has) {
+                    ray.o = v3(park[0 * 64], park[1 * 64], park[2 * 64]);
+                    ray.d = v3(park[3 * 64], park[4 * 64], park[5 * 64]);
+                    ray.maxt = kFloatMax;  // spawn_ray's
+                    // L waits in the ray's slots while the ray is traced
+                    park[0 * 64] = L.x; park[1 * 64] = L.y; park[2 * 64] = L.z;
+                }
+                L = tp = prev_p = a_nee = b_nee = v3(0.f, 0.f, 0.f);
+                prev_pdf = 0.f;
+                rng.state = 0;
+                depth = 1;  // a survivor's (alive needs si.valid)
+                alive = shadow = false;
+            }
+        } while (Two && trip == 1u);
     }
     if (lane_id() == 0 && n_shadow) atomicAdd(ctr + it.seg * 32 + 1, n_shadow);  // statistics only
+    if (Two && lane_id() == 0) {  // bounce 1's counter block: the queue it would have read, and its shadow rays
+        if (n_queue1) atomicAdd(ctr + kCtrStride + it.seg * 32, n_queue1);
+        if (n_shadow1) atomicAdd(ctr + kCtrStride + it.seg * 32 + 1, n_shadow1);
+    }
     MH_BPH_FLUSH(Gen ? 0 : 1);
 }
 
@@ -777,6 +869,7 @@ static hipError_t launch_wavefront_pass(const DScene &S, const IntegratorParams 
     if (!fused)  // the fused first bounce generates its camera rays itself
         hipLaunchKernelGGL(k_wf_raygen, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, S, lm,
                            seed_value, n, plane, out, w, ctr);
+    const variant::BouncePath bp = variant::bounce_path(F, n_bounces, fused_lds_bytes(S));
     for (uint32_t b = 0; b < n_bounces; ++b) {
         uint32_t *c = ctr + kCtrStride * b, *cn = ctr + kCtrStride * (b + 1);
         const int cur = (int)(b & 1);
@@ -788,10 +881,16 @@ static hipError_t launch_wavefront_pass(const DScene &S, const IntegratorParams 
             // after it, ~75 us of idle GPU per chunk)
             if (trace_ev && b == 0) (void)hipEventRecord(trace_ev[0], st);
             const uint32_t gd = grid;
-            variant::select([&](auto Gen) {
-                hipLaunchKernelGGL(k_wf_bounce<Gen>, dim3(gd), dim3(256), fused_lds_bytes(S), st, S,
-                                   in, lm, seed_value, plane, out, pk, cur, seg_cap, c, cn, n, carry, pass, alpha);
-            }, variant::flag(b == 0));
+            const bool two = b == 0 && bp.two;
+            variant::bounce(b == 0, two, [&](auto Gen, auto Two) {
+                // Two: bounces 0 and 1; the launch writes what bounce 1 would have written (its
+                // ping-pong buffer and counter block), and the loop goes on with bounce bp.next
+                hipLaunchKernelGGL((k_wf_bounce<Gen, Two>), dim3(gd), dim3(256),
+                                   fused_lds_bytes(S) + (Two ? variant::kParkBytes : 0u), st, S, in, lm, seed_value,
+                                   plane, out, pk, Two ? (int)(bp.next_buf ^ 1u) : cur, seg_cap, c,
+                                   Two ? ctr + kCtrStride * bp.next : cn, n, carry, pass, alpha);
+            });
+            if (two) b = bp.next - 1;
             if (trace_ev && b + 1 == n_bounces) (void)hipEventRecord(trace_ev[1], st);
             continue;
         }

@@ -11,7 +11,13 @@ state load (or ray generation), closest-hit packet trace, shade, compaction +
 state store, shadow packet trace, tail; plus cycles per iteration, and the
 head of shade (the interaction and the emitter / bsdf / texture ids, up to
 the emitter sample) as a share of shade.  The instrumented kernels run
-somewhat slower than the release build; compare shares within one build."""
+somewhat slower than the release build; compare shares within one build.
+
+The two-bounce generating launch of the path bounce (k_wf_bounce<Gen, Two>,
+the bench's default) reports into the generating group, k_wf_bounce<Gen>: an
+iteration there is one wave-iteration with both its trips, so its trace,
+shade, store and tail phases hold the camera bounce's and bounce 1's cycles
+together.  Build with -DMH_WF_FUSE01=0 to split the one-bounce launches."""
 import argparse
 import ctypes as C
 import json
