@@ -310,7 +310,21 @@ int         mh_device_count(int *count);
 
 /* Scene lifetime. `device` is a HIP ordinal; `stream` a hipStream_t, or NULL
    to let the scene create (and own) a non-blocking stream.  set_stream(NULL)
-   selects the device's default (null) stream. */
+   selects the device's default (null) stream.
+   mh_scene_create checks the whole description before it touches the device
+   (after MH_ERR_NO_DEVICE on a machine without one): a zero film size, an
+   index or a range out of bounds (a face's vertex, a shape's bsdf, emitter or
+   media, the sensor's medium, the environment emitter, a diffuse bsdf's
+   texture, a mesh's faces and vertices, a bitmap's texels, a medium's grid --
+   also when the offset plus the size wraps 64 bits), a table that is NULL
+   although something reads it, a mesh whose has_normals / has_texcoords is set
+   while normals / texcoords is NULL, an HG asymmetry outside (-1, 1), an
+   unknown phase function or pixel format and a depolarised rayleigh medium
+   are MH_ERR_INVALID_ARGUMENT; an area emitter on anything but a rectangle,
+   an unknown shape type, a grid above 2^32 bricked texels and a BVH too deep
+   for the LDS traversal stack are MH_ERR_UNSUPPORTED (INTEGRATION.md lists the
+   messages).  mh_scene_destroy waits for the scene's work and frees everything
+   the scene owns. */
 int mh_scene_create(const mh_scene_desc *desc, int device, void *stream, mh_scene **out);
 int mh_scene_destroy(mh_scene *scene);
 int mh_scene_set_stream(mh_scene *scene, void *stream);

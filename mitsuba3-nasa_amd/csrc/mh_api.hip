@@ -65,9 +65,26 @@ thread_local bool g_keep_error = false;
         }                                                                                   \
     } while (0)
 
+// device memory with one owner: move-only, freed with its owner (a scene's
+// buffers with the scene)
 struct DevBuf {
     void *ptr = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : ptr(o.ptr), bytes(o.bytes) { o.ptr = nullptr; o.bytes = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) {
+            release();
+            ptr = o.ptr;
+            bytes = o.bytes;
+            o.ptr = nullptr;
+            o.bytes = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     hipError_t alloc(size_t n) {
         if (n <= bytes && ptr) return hipSuccess;
         if (ptr) (void)hipFree(ptr);
@@ -123,15 +140,9 @@ struct mh_scene {
         texcoords, faces, texels, media, grid;
     DevBuf phase_tab;  // the tabulated phase functions' tables, one after the other (DScene::phase_tab)
     std::vector<std::vector<PhaseRec>> h_phase_tabs;  // per medium (empty: none set)
-    // a MH_PHASE_BLEND medium's phase function (mh_scene_set_phase_blend): its device record and its tabulated
-    // children's tables (they join phase_tab) and its weight grid in the bricked layout (it joins `grid`,
-    // after the grid_floats floats of the media's own grids)
-    struct BlendHost {
-        bool set = false;
-        DBlend rec{};
-        std::vector<PhaseRec> tab[2];
-        std::vector<float> grid;
-    };
+    // the MH_PHASE_BLEND media's phase functions (mh_scene_set_phase_blend): their tables join phase_tab, their
+    // weight grids join `grid` after the grid_floats floats of the media's own grids
+    using BlendHost = scene::BlendHost;
     std::vector<BlendHost> h_blends;  // per medium
     size_t grid_floats = 0;
     DevBuf work, film_tmp, film4, alpha_px, counters, grad_meta, tmp_a, tmp_b, tmp_c, tmp_d, tmp_e, weights_tmp;
@@ -196,24 +207,54 @@ static int require_device(int device) {
 }
 
 
-int mh_scene_create(const mh_scene_desc *desc, int device, void *stream, mh_scene **out) {
-    ScopedPhase phase_("InitScene");
-    if (!desc || !out) return set_error(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: NULL argument");
-    if (desc->abi_version != MH_ABI_VERSION)
-        return set_error(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: ABI version mismatch");
-    int rc = require_device(device);
-    if (rc) return rc;
-    const mh_sensor &sn = desc->sensor;
-    if (sn.width == 0 || sn.height == 0)
-        return set_error(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: film size must be positive");
-    for (uint32_t i = 0; i < desc->n_emitters; ++i) {
-        const mh_emitter &e = desc->emitters[i];
-        if (e.type == MH_EMITTER_AREA &&
-            (e.shape >= desc->n_shapes || desc->shapes[e.shape].type != MH_SHAPE_RECTANGLE))
-            return set_error(MH_ERR_UNSUPPORTED,
-                             "mh_scene_create: area emitters are supported on rectangles only");
+static int fail(const scene::Error &e) { return set_error(e.code, e.msg); }
+
+// ---- mh_scene_create: the steps, in the order it takes them (mh_scene_build.hpp holds the host arithmetic) ----
+
+// what the host build reads of this library's kernels, the environment and the device
+static scene::Limits scene_limits(int device) {
+    scene::Limits lim;
+    lim.packet_max_prims = wf_packet_max_prims();
+    lim.shade_records = wf_shade_records();
+    lim.bvh4_off = env::bvh4_off();
+    lim.stream_stack = (uint32_t)env::stream_stack(20);
+    lim.stream_threads = wf_blocks(device_cus(device)) * 256u;
+    return lim;
+}
+
+// everything of a scene that is worked out before the device is touched
+struct HostScene {
+    BvhOut bvh;
+    std::vector<uint32_t> key_sp, pairs;
+    scene::Records rec;
+    scene::Facts facts;
+};
+
+static int scene_host_build(const mh_scene_desc *desc, const scene::Limits &lim, HostScene &H) {
+    {
+        const std::vector<BuildPrim> bp = scene::build_prims(*desc);
+        // Leaf size / SAH traversal cost per engine (measured, tools/exp_bvh_leaf.sh):
+        // small scenes take the packet engine, where a wave tests every leaf some
+        // lane reaches and node visits are the serial part -> few, large leaves
+        // (12, C_t = 4); otherwise the per-lane engine (8, C_t = 2).  Leaf counts
+        // <= 31 (5-bit field of the stream engine's stack entries); env overrides.
+        const bool small = bp.size() <= 64;
+        uint32_t max_leaf = (uint32_t)env::bvh_leaf(small ? 12 : 8);
+        float ct = (float)env::bvh_ct(small ? 4.0 : 2.0);
+        ScopedPhase accel_("InitAccel");
+        build_bvh(bp, H.bvh, max_leaf, ct);
     }
-    MH_HIP(hipSetDevice(device));
+    H.key_sp = scene::key_table(H.bvh);
+    H.pairs = scene::pair_records(H.bvh, lim.packet_max_prims);
+    H.rec = scene::records(*desc);
+    H.facts = scene::facts(*desc, H.bvh.nodes.size(), H.bvh.prims.size(), H.bvh.n_prims, H.bvh.depth, lim);
+    if (H.facts.too_deep)
+        return set_error(MH_ERR_UNSUPPORTED, "mh_scene_create: BVH too deep for the LDS traversal stack");
+    return MH_OK;
+}
+
+// the scene object on its stream (the caller's, or one of its own)
+static int scene_open(int device, void *stream, mh_scene **out) {
     mh_scene *s = new (std::nothrow) mh_scene();
     if (!s) return set_error(MH_ERR_OUT_OF_MEMORY, "mh_scene_create: out of host memory");
     s->device = device;
@@ -226,229 +267,56 @@ int mh_scene_create(const mh_scene_desc *desc, int device, void *stream, mh_scen
         }
         s->own_stream = true;
     }
+    *out = s;
+    return MH_OK;
+}
+
+// the BVH and the tables to the device; the host mirrors of what parameter updates edit
+static int scene_upload(mh_scene *s, const mh_scene_desc *desc, HostScene &H) {
     hipStream_t st = s->stream;
-    auto fail = [&](int code, const std::string &m) {
-        mh_scene_destroy(s);
-        return set_error(code, m);
-    };
-
-    // ---- primitives for the BVH (rectangles + mesh triangles) ----
-    std::vector<BuildPrim> bp;
-    for (uint32_t si = 0; si < desc->n_shapes; ++si) {
-        const mh_shape &sh = desc->shapes[si];
-        if (sh.type == MH_SHAPE_RECTANGLE) {
-            BuildPrim p{};
-            const float *m = sh.to_world;
-            for (int a = 0; a < 3; ++a) { p.lo[a] = INFINITY; p.hi[a] = -INFINITY; }
-            const float cs[4][2] = {{-1, -1}, {-1, 1}, {1, -1}, {1, 1}};
-            for (auto &c : cs) {
-                for (int a = 0; a < 3; ++a) {
-                    float q = m[4 * a + 0] * c[0] + m[4 * a + 1] * c[1] + m[4 * a + 3];
-                    p.lo[a] = std::min(p.lo[a], q);
-                    p.hi[a] = std::max(p.hi[a], q);
-                }
-            }
-            memcpy(p.rec, sh.to_object, sizeof(float) * 12);
-            p.shape = si;
-            p.prim = MH_INVALID;
-            p.type = MH_SHAPE_RECTANGLE;
-            bp.push_back(p);
-        } else if (sh.type == MH_SHAPE_MESH) {
-            if ((uint64_t)sh.face_offset + sh.face_count > desc->n_faces ||
-                (uint64_t)sh.vertex_offset + sh.vertex_count > desc->n_vertices)
-                return fail(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: mesh range out of bounds");
-            for (uint32_t f = 0; f < sh.face_count; ++f) {
-                const uint32_t *fi = desc->faces + 3ull * (sh.face_offset + f);
-                const float *v[3];
-                for (int k = 0; k < 3; ++k) {
-                    if (fi[k] >= sh.vertex_count)
-                        return fail(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: face index out of bounds");
-                    v[k] = desc->positions + 3ull * (sh.vertex_offset + fi[k]);
-                }
-                BuildPrim p{};
-                for (int a = 0; a < 3; ++a) {
-                    p.lo[a] = std::min(v[0][a], std::min(v[1][a], v[2][a]));
-                    p.hi[a] = std::max(v[0][a], std::max(v[1][a], v[2][a]));
-                    p.rec[a] = v[0][a];
-                    p.rec[4 + a] = v[1][a] - v[0][a];  // e1 (mesh.h:437)
-                    p.rec[8 + a] = v[2][a] - v[0][a];  // e2
-                }
-                p.shape = si;
-                p.prim = f;
-                p.type = MH_SHAPE_MESH;
-                bp.push_back(p);
-            }
-        } else {
-            return fail(MH_ERR_UNSUPPORTED, "mh_scene_create: unknown shape type");
-        }
-    }
-    BvhOut bvh;
-    {
-        // Leaf size / SAH traversal cost per engine (measured, tools/exp_bvh_leaf.sh):
-        // small scenes take the packet engine, where a wave tests every leaf some
-        // lane reaches and node visits are the serial part -> few, large leaves
-        // (12, C_t = 4); otherwise the per-lane engine (8, C_t = 2).  Leaf counts
-        // <= 31 (5-bit field of the stream engine's stack entries); env overrides.
-        const bool small = bp.size() <= 64;
-        uint32_t max_leaf = (uint32_t)env::bvh_leaf(small ? 12 : 8);
-        float ct = (float)env::bvh_ct(small ? 4.0 : 2.0);
-        ScopedPhase accel_("InitAccel");
-        build_bvh(bp, bvh, max_leaf, ct);
-    }
-    s->bvh_nodes = bvh.n_nodes;
-    s->bvh_prims = bvh.n_prims;
-    s->bvh_depth = bvh.depth;
-    // scene-order key -> (shape, prim) of every primitive (the packet engine
-    // carries only the key of its running hit)
-    std::vector<uint32_t> key_sp(2 * (size_t)bvh.n_prims);
-    for (uint32_t i = 0; i < bvh.n_prims; ++i) {
-        const Prim &q = reinterpret_cast<const Prim *>(bvh.prims.data())[i];
-        key_sp[2 * (size_t)q.info.w] = q.info.x;
-        key_sp[2 * (size_t)q.info.w + 1] = q.info.y;
-    }
-    // pair records of the packet engine: record i interleaves the dwords of
-    // leaf-ordered primitives i and i + 1 (the last one with itself); only
-    // scenes small enough for that engine (wf_packet_max_prims) get them
-    std::vector<uint32_t> pairs(bvh.n_prims <= wf_packet_max_prims() ? 32 * (size_t)bvh.n_prims : 0);
-    for (uint32_t i = 0; i < pairs.size() / 32; ++i) {
-        const uint32_t *a = reinterpret_cast<const uint32_t *>(bvh.prims.data()) + 16 * (size_t)i;
-        const uint32_t *b = reinterpret_cast<const uint32_t *>(bvh.prims.data()) + 16 * (size_t)std::min(i + 1, bvh.n_prims - 1);
-        for (int k = 0; k < 16; ++k) {
-            pairs[32 * (size_t)i + 2 * k] = a[k];
-            pairs[32 * (size_t)i + 2 * k + 1] = b[k];
-        }
-    }
-    if (upload(s->nodes, bvh.nodes.data(), bvh.nodes.size(), st) != hipSuccess ||
-        upload(s->prim_pairs, pairs.data(), pairs.size(), st) != hipSuccess ||
-        upload(s->prims, bvh.prims.data(), bvh.prims.size(), st) != hipSuccess ||
-        upload(s->key_sp, key_sp.data(), key_sp.size(), st) != hipSuccess)
-        return fail(MH_ERR_OUT_OF_MEMORY, "mh_scene_create: BVH upload failed");
-
-    // ---- shading-time records ----
-    std::vector<DShape> shapes(desc->n_shapes);
-    for (uint32_t i = 0; i < desc->n_shapes; ++i) {
-        const mh_shape &a = desc->shapes[i];
-        DShape &b = shapes[i];
-        memset(&b, 0, sizeof(b));
-        b.type = a.type; b.bsdf = a.bsdf; b.emitter = a.emitter; b.face_offset = a.face_offset;
-        b.vertex_offset = a.vertex_offset; b.has_normals = a.has_normals; b.has_texcoords = a.has_texcoords;
-        if (a.bsdf >= desc->n_bsdfs) return fail(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: bsdf index out of bounds");
-        memcpy(b.to_world, a.to_world, sizeof(b.to_world));
-        memcpy(b.frame_s, a.frame_s, 12);
-        memcpy(b.frame_t, a.frame_t, 12);
-        memcpy(b.frame_n, a.frame_n, 12);
-        b.inv_area = a.inv_area;
-        b.interior = a.interior_medium;
-        b.exterior = a.exterior_medium;
-        if ((b.interior != MH_INVALID && b.interior >= desc->n_media) ||
-            (b.exterior != MH_INVALID && b.exterior >= desc->n_media))
-            return fail(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: medium index out of bounds");
-    }
-    // ---- media (heterogeneous.cpp / homogeneous.cpp / grid.cpp) ----
-    std::vector<DMedium> meds(desc->n_media);
-    for (uint32_t i = 0; i < desc->n_media; ++i) {
-        const mh_medium &a = desc->media[i];
-        DMedium &b = meds[i];
-        memset(&b, 0, sizeof(b));
-        b.type = a.type; b.phase = a.phase; b.flags = a.flags;
-        b.g = a.g; b.scale = a.scale; b.sigma_t_const = a.sigma_t_const;
-        // m_max_density = m_scale * m_sigmat->max() (heterogeneous.cpp:163), in float
-        b.maj = a.type == MH_MEDIUM_HOMOGENEOUS ? a.sigma_t_const * a.scale : a.scale * a.max_density;
-        memcpy(b.albedo, a.albedo, 12);
-        memcpy(b.res, a.grid_res, 12);
-        b.grid_offset = 0;   // bricked offset: assigned below
-        memcpy(b.to_local, a.grid_to_local, sizeof(b.to_local));
-        memcpy(b.bbox_min, a.bbox_min, 12);
-        memcpy(b.bbox_max, a.bbox_max, 12);
-        if (a.type == MH_MEDIUM_HETEROGENEOUS &&
-            (a.grid_res[0] == 0 || a.grid_res[1] == 0 || a.grid_res[2] == 0 ||
-             a.grid_offset + (uint64_t)a.grid_res[0] * a.grid_res[1] * a.grid_res[2] > desc->n_grid))
-            return fail(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: volume grid out of bounds");
-        // grid_eval indexes a grid's bricked texels with 32-bit offsets
-        if (a.type == MH_MEDIUM_HETEROGENEOUS && grid_bricked_size(a.grid_res) >= (1ull << 32))
-            return fail(MH_ERR_UNSUPPORTED, "mh_scene_create: volume grid above 2^32 texels");
-        if (a.phase == MH_PHASE_HG && !(a.g > -1.f && a.g < 1.f))
-            return fail(MH_ERR_INVALID_ARGUMENT, "The asymmetry parameter must lie in the interval (-1, 1)!");
-        if (a.phase > MH_PHASE_BLEND)
-            return fail(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: unknown phase function");
-        // rayleigh.cpp:124-126 returns a value that differs from the pdf when
-        // depolarization != 0 (the sampling weight is then not 1)
-        if (a.phase == MH_PHASE_RAYLEIGH && a.g != 0.f)
-            return fail(MH_ERR_INVALID_ARGUMENT,
-                        "mh_scene_create: the rayleigh phase function is supported with depolarization = 0 only: "
-                        "otherwise its value differs from its sampling density and the sampling weight is not 1, "
-                        "which the volumetric integrators here do not carry");
-    }
-    if (desc->sensor.pixel_format > MH_PIXEL_XYZA)
-        return fail(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: unknown pixel format");
+    s->bvh_nodes = H.bvh.n_nodes;
+    s->bvh_prims = H.bvh.n_prims;
+    s->bvh_depth = H.bvh.depth;
+    if (upload(s->nodes, H.bvh.nodes.data(), H.bvh.nodes.size(), st) != hipSuccess ||
+        upload(s->prim_pairs, H.pairs.data(), H.pairs.size(), st) != hipSuccess ||
+        upload(s->prims, H.bvh.prims.data(), H.bvh.prims.size(), st) != hipSuccess ||
+        upload(s->key_sp, H.key_sp.data(), H.key_sp.size(), st) != hipSuccess)
+        return set_error(MH_ERR_OUT_OF_MEMORY, "mh_scene_create: BVH upload failed");
     s->pixel_format = desc->sensor.pixel_format;
-    // density grids in the 4^3-brick device layout (grid_index)
-    std::vector<float> bricked;
-    for (uint32_t i = 0; i < desc->n_media; ++i) {
-        if (desc->media[i].type != MH_MEDIUM_HETEROGENEOUS) continue;
-        meds[i].grid_offset = bricked.size();
-        bricked.resize(bricked.size() + grid_bricked_size(desc->media[i].grid_res));
-        grid_to_bricks(desc->grid_data + desc->media[i].grid_offset, desc->media[i].grid_res,
-                       bricked.data() + meds[i].grid_offset);
-    }
     s->h_media.assign(desc->media, desc->media + desc->n_media);
-    s->h_dmedia = meds;
+    s->h_dmedia = std::move(H.rec.media);
     s->h_phase_tabs.assign(desc->n_media, {});
     s->h_blends.assign(desc->n_media, {});
-    s->grid_floats = bricked.size();
+    s->h_textures = std::move(H.rec.textures);
+    s->h_emitters = std::move(H.rec.emitters);
+    s->grid_floats = H.rec.grid.size();
     s->n_media = desc->n_media;
-    if (desc->sensor.medium != MH_INVALID && desc->sensor.medium >= desc->n_media)
-        return fail(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: sensor medium index out of bounds");
-    std::vector<uint32_t> btype(desc->n_bsdfs), btex(desc->n_bsdfs);
-    for (uint32_t i = 0; i < desc->n_bsdfs; ++i) {
-        btype[i] = desc->bsdfs[i].type;
-        btex[i] = desc->bsdfs[i].reflectance;
-        if (btype[i] == MH_BSDF_DIFFUSE && btex[i] >= desc->n_textures)
-            return fail(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: texture index out of bounds");
-    }
-    s->h_textures.resize(desc->n_textures);
-    for (uint32_t i = 0; i < desc->n_textures; ++i) {
-        const mh_texture &a = desc->textures[i];
-        DTexture &b = s->h_textures[i];
-        memset(&b, 0, sizeof(b));
-        b.type = a.type; b.width = a.width; b.height = a.height; b.channels = a.channels;
-        b.data_offset = a.data_offset; b.filter = a.filter; b.wrap = a.wrap;
-        memcpy(b.value, a.value, 12);
-        memcpy(b.to_uv, a.to_uv, 24);
-        if (a.type == MH_TEX_BITMAP &&
-            a.data_offset + (uint64_t)a.width * a.height * a.channels > desc->n_texels)
-            return fail(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: bitmap data out of bounds");
-    }
-    std::vector<DEmitter> &ems = s->h_emitters;
-    ems.resize(desc->n_emitters);
-    for (uint32_t i = 0; i < desc->n_emitters; ++i) {
-        memset(&ems[i], 0, sizeof(DEmitter));
-        ems[i].type = desc->emitters[i].type;
-        ems[i].shape = desc->emitters[i].shape;
-        memcpy(ems[i].radiance, desc->emitters[i].radiance, 12);
-        memcpy(ems[i].direction, desc->emitters[i].direction, 12);
-        memcpy(ems[i].center, desc->emitters[i].scene_center, 12);
-        ems[i].radius = desc->emitters[i].scene_radius;
-    }
     s->n_textures = desc->n_textures;
     s->n_bsdfs = desc->n_bsdfs;
     s->n_shapes = desc->n_shapes;
     s->n_texels = desc->n_texels;
-    bool ok = upload(s->shapes, shapes.data(), shapes.size(), st) == hipSuccess &&
-              upload(s->bsdf_type, btype.data(), btype.size(), st) == hipSuccess &&
-              upload(s->bsdf_tex, btex.data(), btex.size(), st) == hipSuccess &&
+    const scene::Records &R = H.rec;
+    bool ok = upload(s->shapes, R.shapes.data(), R.shapes.size(), st) == hipSuccess &&
+              upload(s->bsdf_type, R.bsdf_type.data(), R.bsdf_type.size(), st) == hipSuccess &&
+              upload(s->bsdf_tex, R.bsdf_tex.data(), R.bsdf_tex.size(), st) == hipSuccess &&
               upload(s->textures, s->h_textures.data(), s->h_textures.size(), st) == hipSuccess &&
-              upload(s->emitters, ems.data(), ems.size(), st) == hipSuccess &&
+              upload(s->emitters, s->h_emitters.data(), s->h_emitters.size(), st) == hipSuccess &&
               upload(s->positions, desc->positions, 3ull * desc->n_vertices, st) == hipSuccess &&
               upload(s->normals, desc->normals, desc->normals ? 3ull * desc->n_vertices : 0, st) == hipSuccess &&
               upload(s->texcoords, desc->texcoords, desc->texcoords ? 2ull * desc->n_vertices : 0, st) == hipSuccess &&
               upload(s->faces, desc->faces, 3ull * desc->n_faces, st) == hipSuccess &&
               upload(s->texels, desc->texels, desc->n_texels, st) == hipSuccess &&
-              upload(s->media, meds.data(), meds.size(), st) == hipSuccess &&
-              upload(s->grid, bricked.data(), bricked.size(), st) == hipSuccess &&
+              upload(s->media, s->h_dmedia.data(), s->h_dmedia.size(), st) == hipSuccess &&
+              upload(s->grid, R.grid.data(), R.grid.size(), st) == hipSuccess &&
               s->counters.alloc(256 + 1024) == hipSuccess;  // 32 counters + 8 work heads on own lines
-    if (!ok) return fail(MH_ERR_OUT_OF_MEMORY, "mh_scene_create: device upload failed");
+    if (!ok) return set_error(MH_ERR_OUT_OF_MEMORY, "mh_scene_create: device upload failed");
+    return MH_OK;
+}
 
+// the kernels' view of the uploaded scene (BVH2 only, the whole stack in LDS: scene_wide_bvh may change both)
+static void scene_fill(mh_scene *s, const mh_scene_desc *desc, const HostScene &H) {
+    const mh_sensor &sn = desc->sensor;
+    const scene::Facts &F = H.facts;
     DScene &S = s->S;
     S.nodes = s->nodes.as<Node>();
     S.prims = s->prims.as<Prim>();
@@ -469,71 +337,74 @@ int mh_scene_create(const mh_scene_desc *desc, int device, void *stream, mh_scen
     S.phase_tab = nullptr;  // mh_scene_set_phase_table
     S.phase_tab_bytes = S.phase_lds_bytes = 0;
     S.n_media = desc->n_media;
-    S.camera_medium = desc->sensor.medium;
-    S.vol_flags = 0;
-    for (uint32_t i = 0; i < desc->n_shapes; ++i)
-        for (uint32_t mm : {desc->shapes[i].interior_medium, desc->shapes[i].exterior_medium})
-            if (mm != MH_INVALID)
-                S.vol_flags |= desc->media[mm].type == MH_MEDIUM_HOMOGENEOUS ? kVolNeeHomogeneous : kVolHandleNull;
-    for (uint32_t i = 0; i < desc->n_media; ++i)
-        if (desc->media[i].phase == MH_PHASE_RAYLEIGH || desc->media[i].phase == MH_PHASE_TABULATED)
-            S.vol_flags |= kVolPhaseExt;
-        else if (desc->media[i].phase == MH_PHASE_BLEND)
-            S.vol_flags |= kVolPhaseBlend;   // nothing renders until its blend is attached (check_phase_tables)
+    S.camera_medium = sn.medium;
+    S.vol_flags = F.vol_flags;
     S.n_shapes = desc->n_shapes;
     S.n_bsdfs = desc->n_bsdfs;
     S.n_textures = desc->n_textures;
     S.n_vertices = desc->n_vertices;
     S.n_faces = desc->n_faces;
-    {
-        const TabLayout TL = tab_layout(S.n_shapes, S.n_bsdfs, S.n_textures, desc->n_emitters, S.n_vertices,
-                                        S.n_faces, S.normals != nullptr && S.n_vertices,
-                                        S.texcoords != nullptr && S.n_vertices);
-        S.tab_bytes = TL.total <= 16384 ? TL.total : 0u;  // staged into LDS by the shade kernels
-    }
-    S.n_nodes = bvh.n_nodes;
-    S.n_prims = bvh.n_prims;
+    S.tab_bytes = F.tab_bytes;
+    S.n_nodes = H.bvh.n_nodes;
+    S.n_prims = H.bvh.n_prims;
     S.n_emitters = desc->n_emitters;
-    S.inv_n_emitters = 1.f / (float)S.n_emitters;  // inf for 0: never read then
-    S.n_emitters_f = (float)S.n_emitters;
-    S.env_pdf = kInv4Pi * S.inv_n_emitters;
+    S.inv_n_emitters = F.inv_n_emitters;
+    S.n_emitters_f = F.n_emitters_f;
+    S.env_pdf = F.env_pdf;
     S.environment = desc->environment;
-    S.stack_size = bvh.depth + 2;
-    const size_t bvh_bytes = bvh.nodes.size() + bvh.prims.size();
-    S.lds_bytes_bvh = bvh_bytes <= 32768 ? (uint32_t)bvh_bytes : 0u;  // stage into LDS when small
-    // wide BVH for the stream engine when the BVH lives in global memory
-    // (mh_bvh.cpp collapse_bvh4; MH_BVH4=0 keeps BVH2 everywhere)
+    S.stack_size = F.stack_size;
+    S.lds_bytes_bvh = F.lds_bytes_bvh;
     S.nodes4 = nullptr;
     S.qnodes = nullptr;
     S.primsc = nullptr;
-    {
-        // the float BVH4 (round 1); MH_BVH4Q=1: the quantised BVH4 + compact
-        // primitives (round 4, measured slower so far: DESIGN.md §3);
-        // MH_BVH4=0: BVH2
-        if (S.lds_bytes_bvh == 0 && bvh.n_prims > 64 && !env::bvh4_off()) {
-            std::vector<uint8_t> n4, pc;
-            uint32_t cnt4 = 0, depth4 = 0;
-            const bool quant = env::bvh4q() && build_qbvh4(bvh, n4, pc, cnt4, depth4);
-            if (!quant) collapse_bvh4(bvh, n4, cnt4, depth4);
-            const uint32_t stack4 = 3u * depth4 + 2u;
-            if ((size_t)std::max(S.stack_size, stack4) * 256 * 4 <= 65536 &&
-                upload(s->nodes4, n4.data(), n4.size(), st) == hipSuccess &&
-                (!quant || upload(s->primsc, pc.data(), pc.size(), st) == hipSuccess)) {
-                if (quant) {
-                    S.qnodes = reinterpret_cast<const QNode4 *>(s->nodes4.ptr);
-                    S.primsc = reinterpret_cast<const PrimC *>(s->primsc.ptr);
-                } else {
-                    S.nodes4 = reinterpret_cast<const Node4 *>(s->nodes4.ptr);
-                    // MH_PRIMC=1: the compact 48-B triangle records with the float BVH4
-                    if (env::primc()) {
-                        std::vector<uint8_t> qn, pc2;
-                        uint32_t c2 = 0, d2 = 0;
-                        if (build_qbvh4(bvh, qn, pc2, c2, d2) && upload(s->primsc, pc2.data(), pc2.size(), st) == hipSuccess)
-                            S.primsc = reinterpret_cast<const PrimC *>(s->primsc.ptr);
-                    }
+    S.stream_stack = S.stack_size;
+    S.stack_ovf = nullptr;
+    S.ovf_threads = 0;
+    memcpy(S.cam_to_world, sn.to_world, sizeof(S.cam_to_world));
+    memcpy(S.sample_to_camera, sn.sample_to_camera, sizeof(S.sample_to_camera));
+    S.near_clip = sn.near_clip;
+    S.far_clip = sn.far_clip;
+    S.width = sn.width;
+    S.height = sn.height;
+    S.inv_width = F.inv_width;
+    S.inv_height = F.inv_height;
+    S.rfilter = sn.rfilter;
+    S.rfilter_radius = sn.rfilter_radius;
+    memcpy(S.filter_coeff, sn.filter_coeff, sizeof(S.filter_coeff));
+    S.sampler_seed = sn.sampler_seed;
+    S.shade_recs = nullptr;
+}
+
+// Wide BVH for the stream engine when the BVH lives in global memory
+// (mh_bvh.cpp collapse_bvh4; MH_BVH4=0 keeps BVH2 everywhere): the float BVH4
+// (round 1); MH_BVH4Q=1: the quantised BVH4 + compact primitives (round 4,
+// measured slower so far: DESIGN.md §3).  A scene whose wide BVH does not fit
+// or cannot be allocated keeps its BVH2.
+static void scene_wide_bvh(mh_scene *s, const HostScene &H, const scene::Limits &lim) {
+    DScene &S = s->S;
+    hipStream_t st = s->stream;
+    if (H.facts.wide_bvh) {
+        std::vector<uint8_t> n4, pc;
+        uint32_t cnt4 = 0, depth4 = 0;
+        const bool quant = env::bvh4q() && build_qbvh4(H.bvh, n4, pc, cnt4, depth4);
+        if (!quant) collapse_bvh4(H.bvh, n4, cnt4, depth4);
+        const uint32_t stack = scene::wide_stack_size(S.stack_size, depth4);
+        if (stack != 0 && upload(s->nodes4, n4.data(), n4.size(), st) == hipSuccess &&
+            (!quant || upload(s->primsc, pc.data(), pc.size(), st) == hipSuccess)) {
+            if (quant) {
+                S.qnodes = reinterpret_cast<const QNode4 *>(s->nodes4.ptr);
+                S.primsc = reinterpret_cast<const PrimC *>(s->primsc.ptr);
+            } else {
+                S.nodes4 = reinterpret_cast<const Node4 *>(s->nodes4.ptr);
+                // MH_PRIMC=1: the compact 48-B triangle records with the float BVH4
+                if (env::primc()) {
+                    std::vector<uint8_t> qn, pc2;
+                    uint32_t c2 = 0, d2 = 0;
+                    if (build_qbvh4(H.bvh, qn, pc2, c2, d2) && upload(s->primsc, pc2.data(), pc2.size(), st) == hipSuccess)
+                        S.primsc = reinterpret_cast<const PrimC *>(s->primsc.ptr);
                 }
-                S.stack_size = std::max(S.stack_size, stack4);
             }
+            S.stack_size = stack;
         }
     }
     // The stream engine's stack (round 4): the bound 3 * depth4 + 2 of a
@@ -548,47 +419,61 @@ int mh_scene_create(const mh_scene_desc *desc, int device, void *stream, mh_scen
     // 522 / 434 capped at 12-20 entries (5 waves), 534-538 / 446-451 at 6
     // waves (MH_STREAM_WAVES).  MH_STREAM_STACK overrides the cap.
     S.stream_stack = S.stack_size;
-    S.stack_ovf = nullptr;
-    S.ovf_threads = 0;
     if (S.lds_bytes_bvh == 0 && (S.nodes4 || S.qnodes)) {
-        const uint32_t cap = (uint32_t)env::stream_stack(20);
-        if (cap < S.stack_size) {
-            const uint32_t threads = wf_blocks(device_cus(device)) * 256u;
-            if (upload(s->stack_ovf, (const uint32_t *)nullptr, (size_t)(S.stack_size - cap) * threads, st) == hipSuccess) {
-                S.stream_stack = cap;
-                S.stack_ovf = s->stack_ovf.as<uint32_t>();
-                S.ovf_threads = threads;
-            }
+        const size_t words = scene::stack_overflow_words(S.stack_size, lim);
+        if (words && upload(s->stack_ovf, (const uint32_t *)nullptr, words, st) == hipSuccess) {
+            S.stream_stack = lim.stream_stack;
+            S.stack_ovf = s->stack_ovf.as<uint32_t>();
+            S.ovf_threads = lim.stream_threads;
         }
     }
-    if ((size_t)S.stack_size * 256 * 4 + S.lds_bytes_bvh > 65536)
-        return fail(MH_ERR_UNSUPPORTED, "mh_scene_create: BVH too deep for the LDS traversal stack");
-    memcpy(S.cam_to_world, sn.to_world, sizeof(S.cam_to_world));
-    memcpy(S.sample_to_camera, sn.sample_to_camera, sizeof(S.sample_to_camera));
-    S.near_clip = sn.near_clip;
-    S.far_clip = sn.far_clip;
-    S.width = sn.width;
-    S.height = sn.height;
-    S.inv_width = 1.f / (float)S.width;
-    S.inv_height = 1.f / (float)S.height;
-    S.rfilter = sn.rfilter;
-    S.rfilter_radius = sn.rfilter_radius;
-    memcpy(S.filter_coeff, sn.filter_coeff, sizeof(S.filter_coeff));
-    S.sampler_seed = sn.sampler_seed;
-    // shade records of the fused bounce kernels, for the scenes those take (the packet engine's, with
-    // tables that fit LDS): built on the device from the tables uploaded above (same stream), once --
-    // no update call changes geometry, a shape's bsdf or emitter, or a bsdf's type or texture index
-    S.shade_recs = nullptr;
-    if (wf_shade_records() && bvh.n_prims <= wf_packet_max_prims() && S.tab_bytes != 0) {
-        if (upload(s->shade_recs, (const ShadeRec *)nullptr, bvh.n_prims, st) != hipSuccess)
-            return fail(MH_ERR_OUT_OF_MEMORY, "mh_scene_create: shade record allocation failed");
-        S.shade_recs = s->shade_recs.as<ShadeRec>();
-        if (launch_build_shade_recs(S, s->shade_recs.as<ShadeRec>(), st) != hipSuccess)
-            return fail(MH_ERR_HIP, "mh_scene_create: shade record kernel failed");
-    }
+}
+
+// shade records of the fused bounce kernels, for the scenes those take (the packet engine's, with
+// tables that fit LDS): built on the device from the tables uploaded above (same stream), once --
+// no update call changes geometry, a shape's bsdf or emitter, or a bsdf's type or texture index
+static int scene_shade_records(mh_scene *s, const HostScene &H) {
+    if (!H.facts.shade_records) return MH_OK;
+    if (upload(s->shade_recs, (const ShadeRec *)nullptr, H.bvh.n_prims, s->stream) != hipSuccess)
+        return set_error(MH_ERR_OUT_OF_MEMORY, "mh_scene_create: shade record allocation failed");
+    s->S.shade_recs = s->shade_recs.as<ShadeRec>();
+    if (launch_build_shade_recs(s->S, s->shade_recs.as<ShadeRec>(), s->stream) != hipSuccess)
+        return set_error(MH_ERR_HIP, "mh_scene_create: shade record kernel failed");
+    return MH_OK;
+}
+
+static int scene_finish(mh_scene *s) {
     if (hipEventCreate(&s->ev0) != hipSuccess || hipEventCreate(&s->ev1) != hipSuccess)
-        return fail(MH_ERR_HIP, "mh_scene_create: hipEventCreate failed");
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(MH_ERR_HIP, "mh_scene_create: upload sync failed");
+        return set_error(MH_ERR_HIP, "mh_scene_create: hipEventCreate failed");
+    if (hipStreamSynchronize(s->stream) != hipSuccess) return set_error(MH_ERR_HIP, "mh_scene_create: upload sync failed");
+    return MH_OK;
+}
+
+int mh_scene_create(const mh_scene_desc *desc, int device, void *stream, mh_scene **out) {
+    ScopedPhase phase_("InitScene");
+    if (!desc || !out) return set_error(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: NULL argument");
+    if (desc->abi_version != MH_ABI_VERSION)
+        return set_error(MH_ERR_INVALID_ARGUMENT, "mh_scene_create: ABI version mismatch");
+    int rc = require_device(device);
+    if (rc) return rc;
+    if (scene::Error e = scene::validate(*desc)) return fail(e);
+    MH_HIP(hipSetDevice(device));
+    const scene::Limits lim = scene_limits(device);
+    HostScene H;
+    if ((rc = scene_host_build(desc, lim, H))) return rc;
+    mh_scene *s = nullptr;
+    if ((rc = scene_open(device, stream, &s))) return rc;
+    rc = scene_upload(s, desc, H);
+    if (!rc) {
+        scene_fill(s, desc, H);
+        scene_wide_bvh(s, H, lim);
+        rc = scene_shade_records(s, H);
+    }
+    if (!rc) rc = scene_finish(s);
+    if (rc) {
+        mh_scene_destroy(s);  // (leaves the step's message in place)
+        return rc;
+    }
     *out = s;
     return MH_OK;
 }
@@ -598,13 +483,6 @@ int mh_scene_destroy(mh_scene *s) {
     if (s->comm) comm_attach(s->comm, -1);
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
-    for (DevBuf *b : {&s->nodes, &s->nodes4, &s->primsc, &s->stack_ovf, &s->prims, &s->prim_pairs, &s->key_sp, &s->shade_recs, &s->shapes, &s->bsdf_type, &s->bsdf_tex, &s->textures,
-                      &s->emitters, &s->positions, &s->normals, &s->texcoords, &s->faces, &s->texels,
-                      &s->media, &s->grid, &s->phase_tab, &s->work, &s->film_tmp, &s->film4, &s->alpha_px, &s->counters, &s->grad_meta, &s->tmp_a, &s->tmp_b,
-                      &s->tmp_c, &s->tmp_d, &s->tmp_e, &s->weights_tmp, &s->wf_ws, &s->wf_ctr, &s->wf_ws_prb, &s->wf_partial, &s->gw, &s->wf_carry, &s->wf_ws_bmp, &s->wf_ws_det, &s->pvp_log, &s->pvp_main, &s->pvp_ovf, &s->grid_corner, &s->fx_word, &s->bmp_fx,
-                      &s->shard_w, &s->shard_tmp, &s->shard_g, &s->replay_fx, &s->wf_ws2, &s->wf_ws_prb2,
-                      &s->wf_ws_bmp2, &s->wf_partial2, &s->work2, &s->wf_carry2, &s->stack_ovf2})
-        b->release();
     if (s->stream2) {
         (void)hipStreamSynchronize(s->stream2);
         (void)hipStreamDestroy(s->stream2);
@@ -615,7 +493,7 @@ int mh_scene_destroy(mh_scene *s) {
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
-    delete s;
+    delete s;  // frees every DevBuf
     return MH_OK;
 }
 
@@ -745,97 +623,24 @@ int mh_scene_update_medium_phase(mh_scene *s, uint32_t medium, float g) {
     return MH_OK;
 }
 
-// The table of a tabulated phase function: what IrregularContinuousDistribution
-// ::compute_cdf_scalar builds (distr_1d.h:916-978) -- the interval integrals
-// accumulated in double and stored as float, the first and last interval with
-// positive mass, integral = cdf[valid.y], normalization = 1 / integral -- in
-// the PhaseRec layout (mh_device.hpp).  valid = first | last << 16.
-static int build_phase_table(const char *fn, uint32_t n, const float *cost, const float *values,
-                             std::vector<PhaseRec> &tab, uint32_t &valid) {
-    auto bad = [&](const char *why) { return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + why); };
-    if (n < 2) return bad("IrregularContinuousDistribution: needs at least two entries!");
-    if (n > 65536) return bad("more than 65536 entries");
-    tab.assign((size_t)n + 2, PhaseRec{});
-    uint32_t first = MH_INVALID, last = MH_INVALID;
-    double integral = 0.;
-    for (uint32_t i = 0; i < n; ++i) {
-        if (!std::isfinite(cost[i]) || !std::isfinite(values[i])) return bad("entries must be finite");
-        if (cost[i] < -1.f || cost[i] > 1.f) return bad("'cost' must lie in [-1, 1]");
-        if (values[i] < 0.f) return bad("IrregularContinuousDistribution: entries must be non-negative!");
-        PhaseRec &r = tab[1 + i];
-        r.x = cost[i];
-        r.y = values[i];
-        r.c_prev = (float)integral;   // cdf[i - 1]; 0 for i == 0
-        if (i + 1 < n) {
-            if (!(cost[i + 1] > cost[i]))
-                return bad("IrregularContinuousDistribution: node positions must be strictly increasing!");
-            const double value = 0.5 * ((double)cost[i + 1] - (double)cost[i]) * ((double)values[i] + (double)values[i + 1]);
-            integral += value;
-            if (value > 0.) {
-                if (first == MH_INVALID) first = i;
-                last = i;
-            }
-        }
-        r.c = (float)integral;        // cdf[i]; the last node repeats cdf[n - 2]
-    }
-    if (first == MH_INVALID) return bad("IrregularContinuousDistribution: no probability mass found!");
-    const float total = tab[1 + last].c;   // m_integral = cdf[valid.y]
-    if (!(total > 0.f) || !std::isfinite(1.f / total)) return bad("the table's integral is not a normal float");
-    tab[0] = PhaseRec{total, 1.f / total, cost[0], cost[n - 1]};
-    tab[1 + n] = PhaseRec{std::numeric_limits<float>::infinity(), 0.f, total, total};
-    valid = first | (last << 16);
-    return MH_OK;
-}
-
-// The scene's phase data on the device from its (edited) host copies: all
-// tables -- the tabulated media's and the blends' tabulated children's -- and
-// the blends' records (each ahead of its children's tables) in one buffer, the
-// media records with their offsets into it, and, when
-// `regrid`, the grid buffer rebuilt as the media's own grids followed by the
-// blends' weight grids.  Everything is built aside and becomes the scene's only
-// after the last HIP call has succeeded: a failure leaves the old buffers and
-// the records that point into them in place.
+// The scene's phase data on the device from its (edited) host copies, laid out
+// by scene::assemble_phase_data: the tables and blend records in one buffer, the
+// media records with their offsets into it, and, when `regrid`, the grid buffer
+// rebuilt as the media's own grids followed by the blends' weight grids.
+// Everything is built aside and becomes the scene's only after the last HIP call
+// has succeeded: a failure leaves the old buffers and the records that point
+// into them in place.
 static int commit_phase_data(mh_scene *s, const char *fn, std::vector<DMedium> &media,
                              std::vector<std::vector<PhaseRec>> &tabs, std::vector<mh_scene::BlendHost> &blends,
                              bool regrid) {
     MH_HIP(hipSetDevice(s->device));
     MH_HIP(hipStreamSynchronize(s->stream));  // earlier calls may still read the old tables
-    std::vector<PhaseRec> all;
-    uint64_t grid_total = s->grid_floats;
-    for (uint32_t m = 0; m < s->n_media; ++m) {
-        DMedium &b = media[m];
-        if (!tabs[m].empty()) {
-            b.tab_offset = (uint32_t)all.size();
-            b.tab_n = (uint32_t)tabs[m].size() - 2u;
-            all.insert(all.end(), tabs[m].begin(), tabs[m].end());
-        }
-        if (b.phase != MH_PHASE_BLEND) continue;
-        mh_scene::BlendHost &h = blends[m];
-        bool ready = h.set;
-        const size_t at = all.size();
-        if (h.set) all.resize(at + kBlendRecs);   // its DBlend: filled in below, once the children's offsets are known
-        for (int c = 0; c < 2; ++c) {
-            h.rec.tab_offset[c] = h.rec.tab_n[c] = 0;
-            if (!h.set || h.rec.phase[c] != MH_PHASE_TABULATED) continue;
-            if (h.tab[c].empty()) { ready = false; continue; }
-            h.rec.tab_offset[c] = (uint32_t)all.size();
-            h.rec.tab_n[c] = (uint32_t)h.tab[c].size() - 2u;
-            all.insert(all.end(), h.tab[c].begin(), h.tab[c].end());
-        }
-        b.tab_offset = (uint32_t)at;
-        b.tab_n = ready ? 1u : 0u;   // attached: check_phase_tables
-        if (regrid && h.set && h.rec.has_grid) {
-            h.rec.grid_offset = grid_total;
-            grid_total += h.grid.size();
-        }
-        if (h.set) memcpy(static_cast<void *>(&all[at]), &h.rec, sizeof(DBlend));
-    }
-    if (all.size() * sizeof(PhaseRec) >= (1ull << 32))
-        return set_error(MH_ERR_UNSUPPORTED, std::string(fn) + "the phase tables exceed 4 GiB");
+    scene::PhaseData P;
+    if (scene::Error e = scene::assemble_phase_data(fn, media, tabs, blends, regrid, s->grid_floats, P)) return fail(e);
     DevBuf tab_buf, grid_buf;
-    hipError_t e = upload(tab_buf, all.data(), all.size(), s->stream);
+    hipError_t e = upload(tab_buf, P.all.data(), P.all.size(), s->stream);
     if (e == hipSuccess && regrid) {
-        e = grid_buf.alloc(std::max<uint64_t>(grid_total, 4) * sizeof(float));
+        e = grid_buf.alloc(std::max<uint64_t>(P.grid_total, 4) * sizeof(float));
         if (e == hipSuccess && s->grid_floats)
             e = hipMemcpyAsync(grid_buf.ptr, s->grid.ptr, s->grid_floats * sizeof(float), hipMemcpyDeviceToDevice, s->stream);
         for (uint32_t m = 0; m < s->n_media && e == hipSuccess; ++m)
@@ -846,23 +651,17 @@ static int commit_phase_data(mh_scene *s, const char *fn, std::vector<DMedium> &
     if (e == hipSuccess)
         e = hipMemcpyAsync(s->media.ptr, media.data(), sizeof(DMedium) * s->n_media, hipMemcpyHostToDevice, s->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-    if (e != hipSuccess) {
-        tab_buf.release();
-        grid_buf.release();
-        return set_error(MH_ERR_HIP, std::string(fn) + hipGetErrorString(e));
-    }
-    s->phase_tab.release();
-    s->phase_tab = tab_buf;
+    if (e != hipSuccess) return set_error(MH_ERR_HIP, std::string(fn) + hipGetErrorString(e));  // frees tab_buf, grid_buf
+    s->phase_tab = std::move(tab_buf);
     if (regrid) {
-        s->grid.release();
-        s->grid = grid_buf;
+        s->grid = std::move(grid_buf);
         s->S.grid = s->grid.as<float>();
     }
     s->h_dmedia = std::move(media);
     s->h_phase_tabs = std::move(tabs);
     s->h_blends = std::move(blends);
     s->S.phase_tab = s->phase_tab.as<PhaseRec>();
-    s->S.phase_tab_bytes = (uint32_t)(all.size() * sizeof(PhaseRec));
+    s->S.phase_tab_bytes = (uint32_t)(P.all.size() * sizeof(PhaseRec));
     return MH_OK;
 }
 
@@ -874,7 +673,7 @@ int mh_scene_set_phase_table(mh_scene *s, uint32_t medium, uint32_t n, const flo
     if (s->h_dmedia[medium].phase != MH_PHASE_TABULATED) return bad("the medium's phase function is not MH_PHASE_TABULATED");
     std::vector<PhaseRec> tab;
     uint32_t valid = 0;
-    if (int rc = build_phase_table(fn, n, cost, values, tab, valid)) return rc;
+    if (scene::Error e = scene::phase_table(fn, n, cost, values, tab, valid)) return fail(e);
     std::vector<DMedium> media = s->h_dmedia;
     std::vector<std::vector<PhaseRec>> tabs = s->h_phase_tabs;
     std::vector<mh_scene::BlendHost> blends = s->h_blends;
@@ -895,7 +694,7 @@ int mh_scene_set_phase_blend_table(mh_scene *s, uint32_t medium, uint32_t child,
     if (s->h_blends[medium].rec.phase[child] != MH_PHASE_TABULATED) return bad("the child is not MH_PHASE_TABULATED");
     std::vector<PhaseRec> tab;
     uint32_t valid = 0;
-    if (int rc = build_phase_table(fn, n, cost, values, tab, valid)) return rc;
+    if (scene::Error e = scene::phase_table(fn, n, cost, values, tab, valid)) return fail(e);
     std::vector<DMedium> media = s->h_dmedia;
     std::vector<std::vector<PhaseRec>> tabs = s->h_phase_tabs;
     std::vector<mh_scene::BlendHost> blends = s->h_blends;
@@ -904,66 +703,14 @@ int mh_scene_set_phase_blend_table(mh_scene *s, uint32_t medium, uint32_t child,
     return commit_phase_data(s, fn, media, tabs, blends, false);
 }
 
-// a weight grid's n values: finite
-static bool all_finite(const float *v, uint64_t n) {
-    for (uint64_t i = 0; i < n; ++i)
-        if (!std::isfinite(v[i])) return false;
-    return true;
-}
-
 int mh_scene_set_phase_blend(mh_scene *s, uint32_t medium, const mh_phase_blend *b) {
     const char *fn = "mh_scene_set_phase_blend: ";
-    auto bad = [&](const char *why) { return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + why); };
-    if (!s || !b) return bad("NULL argument");
-    if (medium >= s->n_media) return bad("medium index out of bounds");
-    if (s->h_dmedia[medium].phase != MH_PHASE_BLEND) return bad("the medium's phase function is not MH_PHASE_BLEND");
-    for (int c = 0; c < 2; ++c) {
-        if (b->phase[c] > MH_PHASE_TABULATED)
-            return bad("a child must be MH_PHASE_ISOTROPIC, MH_PHASE_HG, MH_PHASE_RAYLEIGH or MH_PHASE_TABULATED "
-                       "(a nested blend is not supported)");
-        if (b->phase[c] == MH_PHASE_HG && !(b->g[c] > -1.f && b->g[c] < 1.f))
-            return bad("The asymmetry parameter must lie in the interval (-1, 1)!");
-        if (b->phase[c] == MH_PHASE_RAYLEIGH && b->g[c] != 0.f)
-            return bad("a rayleigh child is supported with depolarization = 0 only");
-    }
-    const bool has_grid = b->grid_res[0] || b->grid_res[1] || b->grid_res[2];
-    uint64_t n_grid = 0;
-    if (has_grid) {
-        if (!b->grid_res[0] || !b->grid_res[1] || !b->grid_res[2]) return bad("a weight grid needs three non-zero resolutions");
-        if (!b->grid_data) return bad("NULL weight grid data");
-        if (grid_bricked_size(b->grid_res) >= (1ull << 32)) return bad("weight grid above 2^32 texels");
-        n_grid = (uint64_t)b->grid_res[0] * b->grid_res[1] * b->grid_res[2];
-        if (!all_finite(b->grid_data, n_grid) || !all_finite(b->grid_to_local, 12))
-            return bad("the weight grid and its transform must be finite");
-    } else if (!std::isfinite(b->weight)) {
-        return bad("the weight must be finite");
-    }
+    if (!s) return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + "NULL argument");
+    if (scene::Error e = scene::check_blend(fn, s->h_dmedia, medium, b)) return fail(e);
     std::vector<DMedium> media = s->h_dmedia;
     std::vector<std::vector<PhaseRec>> tabs = s->h_phase_tabs;
     std::vector<mh_scene::BlendHost> blends = s->h_blends;
-    mh_scene::BlendHost &h = blends[medium];
-    for (int c = 0; c < 2; ++c) {
-        // a child that stays tabulated keeps its table (a second call: update() of a child's g or of the weight's form)
-        if (!h.set || h.rec.phase[c] != MH_PHASE_TABULATED || b->phase[c] != MH_PHASE_TABULATED) {
-            h.tab[c].clear();
-            h.rec.tab_valid[c] = 0;
-        }
-        h.rec.phase[c] = b->phase[c];
-        h.rec.g[c] = b->g[c];
-    }
-    h.set = true;
-    h.rec.weight = has_grid ? 0.f : b->weight;
-    h.rec.has_grid = has_grid ? 1u : 0u;
-    memset(h.rec.res, 0, sizeof(h.rec.res));
-    memset(h.rec.to_local, 0, sizeof(h.rec.to_local));
-    h.rec.grid_offset = h.rec.pad = 0;
-    h.grid.clear();
-    if (has_grid) {
-        memcpy(h.rec.res, b->grid_res, 12);
-        memcpy(h.rec.to_local, b->grid_to_local, sizeof(h.rec.to_local));
-        h.grid.resize(grid_bricked_size(b->grid_res));
-        grid_to_bricks(b->grid_data, b->grid_res, h.grid.data());
-    }
+    scene::set_blend(blends[medium], *b);
     return commit_phase_data(s, fn, media, tabs, blends, true);
 }
 
@@ -977,7 +724,7 @@ int mh_scene_update_phase_blend_weight(mh_scene *s, uint32_t medium, const float
     mh_scene::BlendHost &h = s->h_blends[medium];
     const uint64_t want = h.rec.has_grid ? (uint64_t)h.rec.res[0] * h.rec.res[1] * h.rec.res[2] : 1ull;
     if (n != want) return bad("size mismatch (a weight grid's x * y * z values, or 1 for a constant weight)");
-    if (!all_finite(data, n)) return bad("the weight must be finite");
+    if (!scene::all_finite(data, n)) return bad("the weight must be finite");
     MH_HIP(hipSetDevice(s->device));
     MH_HIP(hipStreamSynchronize(s->stream));  // earlier calls may still read the old weight
     if (h.rec.has_grid) {
@@ -998,22 +745,8 @@ int mh_scene_update_phase_blend_weight(mh_scene *s, uint32_t medium, const float
     return MH_OK;
 }
 
-// a tabulated medium without its table, or a blend medium without its blend
-// (or without a tabulated child's table): the kernels would read null data
 static int check_phase_tables(const mh_scene *s, const char *fn) {
-    for (uint32_t m = 0; m < s->n_media; ++m) {
-        if (s->h_dmedia[m].phase == MH_PHASE_TABULATED && s->h_dmedia[m].tab_n == 0)
-            return set_error(MH_ERR_INVALID_ARGUMENT, std::string(fn) + ": medium " + std::to_string(m) +
-                                                          " has a tabulated phase function but no table "
-                                                          "(call mh_scene_set_phase_table after mh_scene_create)");
-        if (s->h_dmedia[m].phase == MH_PHASE_BLEND && s->h_dmedia[m].tab_n == 0)
-            return set_error(MH_ERR_INVALID_ARGUMENT,
-                             std::string(fn) + ": medium " + std::to_string(m) +
-                                 (s->h_blends[m].set ? " has a blend phase function with a tabulated child but no table for it "
-                                                       "(call mh_scene_set_phase_blend_table after mh_scene_set_phase_blend)"
-                                                     : " has a blend phase function but no blend "
-                                                       "(call mh_scene_set_phase_blend after mh_scene_create)"));
-    }
+    if (scene::Error e = scene::check_phase_tables(fn, s->h_dmedia, s->h_blends)) return fail(e);
     return MH_OK;
 }
 

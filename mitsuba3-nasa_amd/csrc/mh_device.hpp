@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "../../include/mitsuba_hip.h"
+#include "mh_records.hpp"
 
 namespace mh {
 
@@ -113,15 +114,6 @@ struct alignas(16) PrimC {
 };
 constexpr uint32_t kPrimCRect = 0x80000000u;
 
-struct DShape {                 // shading-time shape record
-    uint32_t type, bsdf, emitter, face_offset;
-    uint32_t vertex_offset, has_normals, has_texcoords, pad;
-    float to_world[12];
-    float frame_s[4], frame_t[4], frame_n[4];
-    float inv_area;
-    uint32_t interior, exterior, pad3;  // media (MH_INVALID = none)
-};
-
 // 64 B: what shading needs of a primitive and what stays the same from scene
 // creation to destruction, by scene-order key (the index of DScene::key_sp).
 // Built on the device by compute_si itself (k_build_shade_recs), so n, s and
@@ -146,77 +138,7 @@ constexpr uint32_t kSrTexcoords = 8u;  // its mesh has texture coordinates
 // vertex_offset fits: the fused kernels take scenes whose tables, vertices included, are within 16 KiB
 constexpr uint32_t kSrVertexShift = 8;
 
-struct DTexture {
-    uint32_t type, width, height, channels;
-    uint64_t data_offset;
-    uint32_t filter, wrap;
-    float value[4];
-    float to_uv[8];
-};
-
-struct DEmitter {
-    uint32_t type, shape, pad0, pad1;
-    float radiance[4];
-    float direction[4];
-    float center[3], radius;   // constant / directional: scene bounding sphere
-};
-
-// One record of a tabulated phase function's table (DScene::phase_tab; built
-// by mh_scene_set_phase_table from IrregularContinuousDistribution's nodes,
-// pdf and cdf, distr_1d.h:916-978).  A medium's table is a header
-// {integral, normalization, range.x, range.y} at tab_offset, then one record
-// per node i at tab_offset + 1 + i: {nodes[i], pdf[i], cdf[i - 1] (0 for
-// i == 0), cdf[i] (cdf[n - 2] for the last node)}, then one more record with
-// x = +inf that a search for a value beyond the range may read.  Interval i
-// is records i and i + 1: one 32-byte fetch after the search.
-struct alignas(16) PhaseRec { float x, y, c_prev, c; };
-
-struct DMedium {
-    uint32_t type, phase, flags;
-    uint32_t tab_offset;                  // tabulated phase: first record (the header) in DScene::phase_tab;
-                                          // blend: where its DBlend starts there
-    float g, scale, maj, sigma_t_const;   // maj = scale * max(grid) (heterogeneous.cpp:163)
-    float albedo[4];
-    uint32_t res[4];
-    uint64_t grid_offset;   // first float of the medium's bricked grid (grid_index)
-    uint32_t tab_n;         // tabulated phase: nodes (0: no table yet); blend: 1 once it is attached
-    uint32_t tab_valid;     // its first | last << 16 interval with positive mass (m_valid)
-    float to_local[12];
-    float bbox_min[4], bbox_max[4];
-    static constexpr bool kFarLookups = false;  // grid_setup: sigma_t is looked up inside the medium's box only
-};
-
-// A MH_PHASE_BLEND medium's phase function (BlendPhaseFunction,
-// src/phase/blendphase.cpp, two children; mh_scene_set_phase_blend): the
-// children as the fields of DMedium that phase_eval / phase_sample read, and
-// weight_0 -- a constant, or (has_grid) a one-channel grid of its own in
-// DScene::grid, read by grid_eval through res / grid_offset / to_local.  It
-// lies in DScene::phase_tab at DMedium::tab_offset, in the place of 8 records,
-// ahead of its tabulated children's tables: DScene keeps its size (the
-// kernels of scenes without a blend keep their registers), and k_vol_sched
-// stages it into LDS with the tables.
-struct alignas(16) DBlend {
-    uint32_t phase[2];
-    float g[2];
-    uint32_t tab_offset[2], tab_n[2], tab_valid[2];   // tabulated children: as DMedium's
-    float weight;
-    uint32_t has_grid;
-    uint32_t res[4];
-    uint64_t grid_offset, pad;
-    float to_local[12];
-    static constexpr bool kFarLookups = true;   // grid_setup: looked up outside its box (the medium's scatter points)
-};
-static_assert(sizeof(DBlend) == 8 * sizeof(PhaseRec), "a DBlend takes 8 records of DScene::phase_tab");
-constexpr uint32_t kBlendRecs = 8;
-
-// PRBVolpathIntegrator.prepare_scene (prbvolpath.py:76-89), from the media of the shapes
-constexpr uint32_t kVolHandleNull = 1u;       // some medium is heterogeneous
-constexpr uint32_t kVolNeeHomogeneous = 2u;   // some medium is homogeneous
-// not prepare_scene's: some medium's phase function is rayleigh or tabulated
-// (launch_vol_sched: volpath's machine with those branches; else the one without)
-constexpr uint32_t kVolPhaseExt = 4u;
-// some medium's phase function is a blend: the kernels compiled with it (kPhBlend, mh_shading.hpp)
-constexpr uint32_t kVolPhaseBlend = 8u;
+// DShape, DTexture, DEmitter, PhaseRec, DMedium, DBlend and the kVol* flags: mh_records.hpp (shared with the host build)
 
 struct DScene {                 // kernel argument (by value)
     const Node *nodes;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/mitsuba_hip.h"
+#include "mh_scene_build.hpp"
 #include "mh_slots.hpp"
 #include "mh_variant.hpp"
 
@@ -69,26 +70,7 @@ __host__ __device__ inline const int32_t *emitter_slot_table(const int32_t *slot
                        : nullptr;
 }
 
-// ---- BVH builder (host, binned SAH) --------------------------------------
-struct BuildPrim {
-    float lo[3], hi[3];   // world AABB
-    float rec[12];        // Prim a/b/c payload
-    uint32_t shape, prim, type;
-};
-struct BvhOut {
-    std::vector<uint8_t> nodes;  // sizeof(Node) * n_nodes
-    std::vector<uint8_t> prims;  // sizeof(Prim) * n_prims (reordered)
-    uint32_t n_nodes = 0, n_prims = 0, depth = 0;
-};
-// max_leaf <= 31 (5-bit leaf count of the per-lane stream engine's stack entries)
-void build_bvh(const std::vector<BuildPrim> &in, BvhOut &out, uint32_t max_leaf = 4, float trav_cost = 1.0f);
-// BVH4 collapsed from a BVH2 (greedy: open the largest-area inner child until
-// four children); depth4 = max Node4 nesting
-void collapse_bvh4(const BvhOut &b2, std::vector<uint8_t> &nodes4, uint32_t &n4, uint32_t &depth4);
-// the same BVH4 quantised (QNode4, children-contiguous order) + compact
-// primitive records (PrimC); false when a box cannot be quantised
-bool build_qbvh4(const BvhOut &b2, std::vector<uint8_t> &qnodes, std::vector<uint8_t> &primsc, uint32_t &n4,
-                 uint32_t &depth4);
+// BuildPrim, BvhOut and the BVH builders of mh_bvh.cpp: mh_scene_build.hpp
 
 // ---- kernel launchers (mh_kernels.hip) -------------------------------------
 size_t lds_bytes(const DScene &S, uint32_t block);
@@ -188,9 +170,7 @@ inline float ordered_key_to_float(uint32_t k) {
     c.u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
     return c.f;
 }
-// linear (z, y, x) grid -> 4^3-brick device layout (grid_index, mh_shading.hpp)
-uint64_t grid_bricked_size(const uint32_t res[3]);
-void grid_to_bricks(const float *src, const uint32_t res[3], float *dst);
+// linear (z, y, x) grid -> 4^3-brick device layout (grid_index, grid_to_bricks: mh_records.hpp)
 hipError_t launch_grid_to_bricks(const float *src, const uint32_t res[3], float *dst, hipStream_t st);
 hipError_t launch_accumulate(float *dst, const float *src, uint64_t n, hipStream_t st);  // dst += src
 // grid sigma_t gradient: per-cell corner block (GradArgs::corner, corner_floats of mh_slots.hpp) -> (z, y, x) gradient (+=)

@@ -1140,21 +1140,6 @@ __global__ void k_accumulate(float *__restrict__ dst, const float *__restrict__ 
     if (i < n) dst[i] += src[i];
 }
 
-// the device layout of a density grid (mh_shading.hpp grid_setup: 4^3
-// bricks), in floats
-uint64_t grid_bricked_size(const uint32_t res[3]) {
-    return (uint64_t)((res[0] + 3) / 4) * ((res[1] + 3) / 4) * ((res[2] + 3) / 4) * 64u;
-}
-
-void grid_to_bricks(const float *src, const uint32_t res[3], float *dst) {
-    const int32_t rx = (int32_t)res[0], ry = (int32_t)res[1], rz = (int32_t)res[2];
-    std::fill(dst, dst + grid_bricked_size(res), 0.f);
-    for (int32_t z = 0; z < rz; ++z)
-        for (int32_t y = 0; y < ry; ++y)
-            for (int32_t x = 0; x < rx; ++x)
-                dst[grid_index(x, y, z, rx, ry)] = src[((uint64_t)z * ry + y) * rx + x];
-}
-
 __global__ void k_grid_to_bricks(const float *__restrict__ src, int32_t rx, int32_t ry, int32_t rz,
                                  float *__restrict__ dst) {
     const uint64_t n = (uint64_t)rx * ry * rz;

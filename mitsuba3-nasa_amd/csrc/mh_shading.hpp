@@ -271,29 +271,8 @@ __host__ __device__ inline size_t stream_lds_bytes(const DScene &S, uint32_t blo
 // vertices, emitter -> shape); from LDS each link costs ~100 cycles instead
 // of an L2 round trip.  The returned scene view points into LDS; callers
 // instantiate this unconditionally (template) so hipcc emits ds_read.
-// Layout and size: tab_layout (host and device agree).
+// Layout and size: tab_layout (mh_records.hpp; host and device agree).
 // ---------------------------------------------------------------------------
-struct TabLayout {
-    uint32_t shapes, bsdf_type, bsdf_tex, textures, emitters, positions, normals, texcoords, faces, total;
-};
-__host__ __device__ inline TabLayout tab_layout(uint32_t n_shapes, uint32_t n_bsdfs, uint32_t n_textures,
-                                                uint32_t n_emitters, uint32_t n_vertices, uint32_t n_faces,
-                                                bool normals, bool texcoords) {
-    auto al = [](uint32_t x) { return (x + 15u) & ~15u; };
-    TabLayout L;
-    uint32_t o = 0;
-    L.shapes = o; o += al(n_shapes * (uint32_t)sizeof(DShape));
-    L.bsdf_type = o; o += al(n_bsdfs * 4u);
-    L.bsdf_tex = o; o += al(n_bsdfs * 4u);
-    L.textures = o; o += al(n_textures * (uint32_t)sizeof(DTexture));
-    L.emitters = o; o += al(n_emitters * (uint32_t)sizeof(DEmitter));
-    L.positions = o; o += al(n_vertices * 12u);
-    L.normals = o; o += normals ? al(n_vertices * 12u) : 0u;
-    L.texcoords = o; o += texcoords ? al(n_vertices * 8u) : 0u;
-    L.faces = o; o += al(n_faces * 12u);
-    L.total = o;
-    return L;
-}
 
 MH_DEV void lds_copy(uint8_t *dst, const void *src, uint32_t bytes) {
     const uint32_t *s = reinterpret_cast<const uint32_t *>(src);
@@ -1587,9 +1566,7 @@ MH_DEV V3 area_sample_direction(const DScene &S, uint32_t em, V3 ref_p, float sx
     return vdiv(v3(e.radiance[0], e.radiance[1], e.radiance[2]), ds.pdf);
 }
 
-constexpr float kInv4Pi = 0.07957747154594766788f;
-
-// warp::square_to_uniform_sphere (core/warp.h:250-255)
+// warp::square_to_uniform_sphere (core/warp.h:250-255); kInv4Pi: mh_records.hpp
 MH_DEV V3 square_to_uniform_sphere(float sx, float sy) {
     float z = __builtin_fmaf(-2.f, sy, 1.f);
     float r = __builtin_sqrtf(fmaxf(__builtin_fmaf(-z, z, 1.f), 0.f));
@@ -2748,18 +2725,7 @@ struct MEI {
     V3 fs, ft, fn;   // Frame3f(ray.d); wi = (0, 0, -1) local
 };
 
-// Device layout of a density grid (the host API and gradients keep the
-// reference's linear (z, y, x) layout; values are unchanged, so lookups are
-// bit-exact either way).
-//
-// 4 x 4 x 4 bricks of 64 floats (256 B), bricks x-fastest, texels x-fastest
-// inside a brick.  (Round 5 measured apron tiles -- every lookup in one
-// 128-B line at 3.6x the texels -- as neutral: DESIGN.md section 9.)
-__host__ __device__ __forceinline__ uint64_t grid_index(int32_t x, int32_t y, int32_t z, int32_t rx, int32_t ry) {
-    const uint32_t nbx = (uint32_t)(rx + 3) >> 2, nby = (uint32_t)(ry + 3) >> 2;
-    const uint64_t brick = ((uint64_t)((uint32_t)z >> 2) * nby + ((uint32_t)y >> 2)) * nbx + ((uint32_t)x >> 2);
-    return brick * 64u + ((((uint32_t)z & 3u) << 4) | (((uint32_t)y & 3u) << 2) | ((uint32_t)x & 3u));
-}
+// (the bricked device layout of a density grid: grid_index, mh_records.hpp)
 // [drjit] Texture3f::eval_nonaccel, linear, clamp, 1 channel (grid.cpp:545-558),
 // in three parts: the tap offsets and weights, the 8 loads, the interpolation
 struct GridLookup {
